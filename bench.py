@@ -2,7 +2,10 @@
 """bench.py -- the reference's headline metric on MI355X: BPR-MF SGD samples/sec (+ ItemKNN cosine build
 seconds) on an ML-20M-shaped synthetic URM (138 493 x 26 744, ~20 M interactions), k=128, batch 1000.
 
-  python bench.py --gpus N --steps K --warmup W [--workload ml20m|ml1m|netflix]
+  python bench.py --gpus N --steps K --warmup W [--workload ml20m|ml1m|netflix] [--dump-outputs DIR] [--full]
+  A plain run measures the headline alone: it builds the URM and the model, runs W warm-up and K timed steps, writes the outputs
+  of the last timed step (--dump-outputs) and prints the line.  --full adds everything else below: the ItemKNN builds, IALS, the
+  other hot paths, the per-launch roofline of the headline kernel and the CPU baselines.
   N > 1:  either as above -- bench.py then starts the N ranks itself (launch_ranks: one process per GPU, refuses to run when fewer
           than N devices are visible) -- or under python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
           127.0.0.1 ... bench.py --gpus N ... (WORLD_SIZE must then equal N).
@@ -17,7 +20,7 @@ all-gather); its wall seconds at this N are in `extra.itemknn` (strong scaling o
 resident on every rank's device, the same definition at N = 1).  `--workload netflix` runs both on BASELINE.json's
 configs[3] shape (480 189 x 17 770, 100 M interactions).
 
-One JSON line is printed by rank 0.  `roofline` is for the dominant kernel of the headline metric (mf_batch_kernel):
+One JSON line is printed by rank 0.  `ms_per_step` is the wall time of one timed step.  With --full: `roofline` is for the dominant kernel of the headline metric (mf_batch_kernel):
 algorithmic bytes of one launch (batch_size x 24*k B) over the average launch duration measured with the
 dispatch's own HIP start/stop events on the handle's stream in a separate, untimed call of the same run.  `extra.paths`
 carries one roofline block per other hot path (SLIM-BPR, FunkSVD, IALS, scoring).  `cpu_baseline` is the reference's own
@@ -58,13 +61,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="ml20m", choices=["ml20m", "ml1m", "netflix"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the model the last timed step left behind as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (the --no-* options below select among them); "
+                    "without it a run measures the headline BPR-MF epochs only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sim", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of each CPU baseline leg")
     ap.add_argument("--no-extras", action="store_true", help="skip the other hot paths (FunkSVD, SLIM-BPR, IALS, scoring, replicas)")
     ap.add_argument("--no-paths", action="store_true", help="skip the other hot paths but keep the emulated 8-way ItemKNN build")
     ap.add_argument("--no-ials", action="store_true", help="skip the row-sharded IALS epoch (BASELINE config 5)")
-    ap.add_argument("--no-netflix", action="store_true", help="skip the Netflix-shape ItemKNN build (BASELINE config 4; part of every N > 1 run and of the default N = 1 run)")
+    ap.add_argument("--no-netflix", action="store_true", help="skip the Netflix-shape ItemKNN build (BASELINE config 4; part of every --full run)")
     return ap.parse_args()
 
 
@@ -767,6 +773,22 @@ def fit_rows(urm, out):
     return out
 
 
+DUMP_USER_ROWS = 65536
+
+
+def dump_outputs(mf, folder):
+    """--dump-outputs: the model the last timed step left behind, as a caller of the epochs reads it (get_factors), for comparing
+    two builds output for output.  item_factors.npy is ITEM_factors whole; user_factors_sample.npy holds the USER_factors rows of a
+    fixed seeded sample of DUMP_USER_ROWS users in ascending order (all rows of a smaller URM), which keeps the dump below 64 MB at
+    every workload (USER_factors alone is 71 MB at the ML-20M shape)."""
+    import numpy as np
+    U, V = mf.get_factors()
+    rows = np.sort(np.random.default_rng(0).choice(U.shape[0], min(DUMP_USER_ROWS, U.shape[0]), replace=False))
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "item_factors.npy"), V)
+    np.save(os.path.join(folder, "user_factors_sample.npy"), U[rows])
+
+
 DRIVER_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
                "config")
 EXTRA_FILE = "bench_extra.json"
@@ -791,9 +813,10 @@ def compact_line(out):
     else the run measured is in EXTRA_FILE (and, as one earlier line, on stderr).  Stays far below 8 KB whatever the sections hold
     (tests/test_bench_line.py builds it from a recorded run)."""
     line = {k: _sig(out[k]) for k in DRIVER_KEYS if k in out}
-    line["roofline"] = _slim(out.get("roofline", {}), ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us",
-                                                      "algorithmic_bytes_per_launch", "timed_launches"))
-    line["roofline"].setdefault("traffic", None)
+    if "roofline" in out:
+        line["roofline"] = _slim(out["roofline"], ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_us",
+                                                   "algorithmic_bytes_per_launch", "timed_launches"))
+        line["roofline"].setdefault("traffic", None)
     if "cpu_baseline" in out:
         line["cpu_baseline"] = _slim(out["cpu_baseline"], ("value", "unit", "cores", "kind", "host_cpu_count"))
         line["cpu_baseline"]["sample"] = str(out["cpu_baseline"].get("sample", ""))[:160]
@@ -1308,6 +1331,10 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_sim = args.no_ials = args.no_extras = args.no_paths = args.no_cpu_baseline = args.no_netflix = True
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(launch_ranks(args))                   # the ranks come back through main() with WORLD_SIZE set
@@ -1367,22 +1394,26 @@ def main():
     elapsed = net.max(elapsed)
     total_samples = args.steps * per_epoch * world
     value = total_samples / elapsed
-    # per-launch duration of the dominant kernel: a SEPARATE, untimed call whose mini-batch launches carry their own HIP
-    # start/stop events on the handle's stream (plain launches instead of graph replay; not part of `value`)
-    mf.set_profiling(5 * n_batches)
-    mf.epochIteration_Cython(5)
-    pst = mf.stats()
-    mf.set_profiling(0)
-    avg_launch_s = (pst["kernel_ms"] / max(1, pst["n_timed"])) * 1e-3
-    bytes_per_launch = st["algorithmic_bytes"] / max(1, st["n_launches"])
-    achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
-    traffic, traffic_source = pmc_traffic("mf_batch_kernel")
-    roofline = {"bound": "hbm", "kernel": "mf_batch_kernel", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                "algorithmic_bytes_per_launch": bytes_per_launch, "avg_launch_us": avg_launch_s * 1e6,
-                "timed_launches": pst["n_timed"],
-                "whole_epoch_achieved_GBps": st["algorithmic_bytes"] / (st["call_ms"] * 1e-3) / 1e9,
-                "whole_epoch_frac": st["algorithmic_bytes"] / (st["call_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(mf, args.dump_outputs)
+    roofline = None
+    if args.full:
+        # per-launch duration of the dominant kernel: a SEPARATE, untimed call whose mini-batch launches carry their own HIP
+        # start/stop events on the handle's stream (plain launches instead of graph replay; not part of `value`)
+        mf.set_profiling(5 * n_batches)
+        mf.epochIteration_Cython(5)
+        pst = mf.stats()
+        mf.set_profiling(0)
+        avg_launch_s = (pst["kernel_ms"] / max(1, pst["n_timed"])) * 1e-3
+        bytes_per_launch = st["algorithmic_bytes"] / max(1, st["n_launches"])
+        achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+        traffic, traffic_source = pmc_traffic("mf_batch_kernel")
+        roofline = {"bound": "hbm", "kernel": "mf_batch_kernel", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                    "algorithmic_bytes_per_launch": bytes_per_launch, "avg_launch_us": avg_launch_s * 1e6,
+                    "timed_launches": pst["n_timed"],
+                    "whole_epoch_achieved_GBps": st["algorithmic_bytes"] / (st["call_ms"] * 1e-3) / 1e9,
+                    "whole_epoch_frac": st["algorithmic_bytes"] / (st["call_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
     mf.close()
 
     note("headline: %.1f M samples/s" % (value / 1e6))
@@ -1414,7 +1445,9 @@ def main():
            "config": {"workload": "BPR-MF epoch (%d mini-batches x 1000 on-device samples), k=128, sgd, on synthetic %s URM "
                                   "%dx%d nnz=%d; replicas (one independent model per GPU)" % (n_batches, args.workload, n_users, n_items, urm.nnz),
                       "batch_size": BATCH, "n_factors": K_FACTORS, "parallelism": "replicas x%d" % world},
-           "roofline": roofline, "extra": extra}
+           "extra": extra}
+    if roofline is not None:
+        out["roofline"] = roofline
 
     note("ials section done")
     cpu_jobs = []
@@ -1473,7 +1506,7 @@ def main():
                 out["extra"].setdefault("cpu_legs_error", "")
                 out["extra"]["cpu_legs_error"] += "%s: %r; " % (tag, exc)
     # one compact row per path at the TOP level (value, unit, fraction of the bound, CPU baseline of the same run)
-    table = {"bpr_mf_k128_batch1000_one_model": {"value": value, "unit": "samples/s", "bound": "hbm", "frac": roofline["frac"],
+    table = {"bpr_mf_k128_batch1000_one_model": {"value": value, "unit": "samples/s", "bound": "hbm", "frac": (roofline or {}).get("frac"),
                                                  "cpu_value": out.get("cpu_baseline", {}).get("value"), "cpu_kind": out.get("cpu_baseline", {}).get("kind")}}
     for name, blk in out["extra"].get("paths", {}).items():
         if not isinstance(blk, dict):

@@ -81,6 +81,38 @@ def euclidean_row_weights():
     np.savez_compressed(os.path.join(HERE, "euclidean_row_weights.npz"), **out)
 
 
+def oracle_vs_reference():
+    """The inputs and reference outputs of tests/test_oracle_vs_reference.py's Euclidean and similarityMatrixTopK cases (reference
+    Compute_Similarity_Euclidean and Base/Recommender_utils.similarityMatrixTopK), outputs in the reference's own dtype.
+    `python make_golden.py oracle_vs_reference` writes this fixture alone."""
+    from recsys2019_deeplearning_evaluation_amd.synthetic import synthetic_urm
+    EUC = ref_loader.load_python_reference("Base.Similarity.Compute_Similarity_Euclidean", "Compute_Similarity_Euclidean")
+    topk = ref_loader.load_python_reference("Base.Recommender_utils", "similarityMatrixTopK")
+    X = synthetic_urm(150, 90, 2500, seed=5, values="real")
+    out = pack_csr("X", X)
+    for mode in ("lin", "log", "exp"):
+        for n, kw in enumerate((dict(normalize=False, normalize_avg_row=False, shrink=0), dict(normalize=True, normalize_avg_row=True, shrink=3))):
+            out["euc_%s_%d" % (mode, n)] = quiet(lambda: EUC(X, topK=10, similarity_from_distance_mode=mode, **kw).compute_similarity()).toarray()
+    Xw = synthetic_urm(120, 120, 2600, seed=8, values="real")
+    out.update(pack_csr("Xw", Xw))
+    out["w"] = np.random.default_rng(8).uniform(0.1, 3.0, 120)
+    for dtype in ("float32", "float64"):
+        w = out["w"].astype(dtype)
+        for n, kw in enumerate((dict(normalize=False, normalize_avg_row=False, shrink=0, similarity_from_distance_mode="lin"),
+                                dict(normalize=True, normalize_avg_row=True, shrink=2, similarity_from_distance_mode="log"))):
+            out["eucw_%s_%d" % (dtype, n)] = quiet(lambda: EUC(Xw, topK=12, row_weights=w, **kw).compute_similarity()).toarray()
+    rng = np.random.default_rng(2)
+    A = sps.random(70, 70, 0.4, random_state=np.random.RandomState(2), format="csr", dtype=np.float32)
+    A.data = rng.standard_normal(A.nnz).astype(np.float32)
+    out.update(pack_csr("A", A))
+    for k in (1, 6, 70):
+        out["topk_sparse_%d" % k] = quiet(lambda: topk(A.copy(), k=k, verbose=False)).toarray()
+        want = quiet(lambda: topk(A.toarray(), k=k, verbose=False))
+        out["topk_dense_%d" % k] = want.toarray() if sps.issparse(want) else np.asarray(want)
+    out["cases"] = np.array(json.dumps([]))
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_reference.npz"), **out)
+
+
 def main():
     assert build_ref.build(), "reference sources not available: run this where /root/reference exists"
     MF, SLIM, SIM = ref_loader.load("mf"), ref_loader.load("slim"), ref_loader.load("sim")
@@ -266,6 +298,7 @@ def main():
     out["cases"] = np.array(json.dumps(cases))
     np.savez_compressed(os.path.join(HERE, "euclidean.npz"), **out)
     euclidean_row_weights()
+    oracle_vs_reference()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
@@ -274,5 +307,7 @@ def main():
 if __name__ == "__main__":
     if sys.argv[1:] == ["euclidean_row_weights"]:
         euclidean_row_weights()
+    elif sys.argv[1:] == ["oracle_vs_reference"]:
+        oracle_vs_reference()
     else:
         main()

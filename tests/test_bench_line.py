@@ -56,3 +56,35 @@ def test_a_huge_side_section_cannot_lengthen_the_line():
 def test_numbers_carry_five_significant_digits():
     assert bench._sig(213053896.0011929) == 213050000.0 and bench._sig(0.08492590706) == 0.084926
     assert bench._sig(float("nan")) is None and bench._sig(7) == 7 and bench._sig(True) is True and bench._sig("s") == "s"
+
+
+def test_dump_outputs_of_the_ml20m_shape_stay_under_64_mb_and_repeat(tmp_path):
+    """--dump-outputs writes what a caller of the timed epochs reads (get_factors) in float32 / float64, at most 64 MB at the
+    largest user count a workload has, and the same rows from run to run (two builds are compared file for file)."""
+    import numpy as np
+
+    class Model:
+        def __init__(self, n_users, n_items):
+            rng = np.random.default_rng(n_users)
+            self.U = rng.random((n_users, bench.K_FACTORS), dtype=np.float32)
+            self.V = rng.random((n_items, bench.K_FACTORS), dtype=np.float32)
+
+        def get_factors(self):
+            return self.U, self.V
+
+    for n_users, n_items in ((480189, 17770), (138493, 26744), (6040, 3706)):        # netflix, ml20m, ml1m shapes
+        m = Model(n_users, n_items)
+        for run in ("a", "b"):
+            bench.dump_outputs(m, str(tmp_path / run))
+        files = sorted(p.name for p in (tmp_path / "a").iterdir())
+        assert files == ["item_factors.npy", "user_factors_sample.npy"]
+        assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+        for f in files:
+            a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+            assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        assert np.array_equal(np.load(tmp_path / "a" / "item_factors.npy"), m.V)
+        sample = np.load(tmp_path / "a" / "user_factors_sample.npy")
+        assert sample.shape == (min(n_users, bench.DUMP_USER_ROWS), bench.K_FACTORS)
+        if n_users <= bench.DUMP_USER_ROWS:
+            assert np.array_equal(sample, m.U)
+
