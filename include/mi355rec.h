@@ -389,6 +389,34 @@ int mi355rec_ials_get_stats(mi355rec_ials_t h, mi355rec_stats *stats);
 void mi355rec_ials_destroy(mi355rec_ials_t h);
 
 /* ------------------------------------------------------------------------------------------------------
+ * SLIM ElasticNet  (SLIM_ElasticNet/SLIMElasticNetRecommender.py:41-149: one sklearn ElasticNet per item, sparse coordinate
+ * descent with selection='random', _cd_fast.pyx sparse_enet_coordinate_descent) as coordinate descent on the Gram matrix
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_slimen *mi355rec_slimen_t;
+
+/* URM_train (n_users x n_items) in both layouts, CSR and CSC, float32 values, sorted indices.  Builds G = X^T X (n_items^2 float32,
+ * never leaves the device) and diag = column sums of squares; fails with MI355REC_E_INVALID when G does not fit the free memory. */
+int mi355rec_slimen_create(mi355rec_slimen_t *out, int32_t n_users, int32_t n_items, const int32_t *row_ptr, const int32_t *row_idx,
+                           const float *row_val, const int32_t *col_ptr, const int32_t *col_idx, const float *col_val);
+/* Fits the targets [start_item, end_item): seeds[t] is the solver seed of target start_item + t (np.random.randint(0, 2**31 - 1),
+ * drawn by the caller in item order); alpha, l1_ratio, positive, max_iter and tol as sklearn's ElasticNet (l1 = alpha * l1_ratio *
+ * n_users, l2 = alpha * (1 - l1_ratio) * n_users); topK: per target the min(nnz - 1, topK) largest coefficients are kept
+ * (SLIMElasticNetRecommender.py:107-111); topK = -1 keeps every nonzero coefficient (diagnostics: the whole solution). */
+int mi355rec_slimen_fit(mi355rec_slimen_t h, int32_t start_item, int32_t end_item, const uint32_t *seeds, double alpha, double l1_ratio,
+                        int32_t positive, int32_t topK, int32_t max_iter, double tol);
+/* Results of the last fit, per target t of its range: counts[t] kept coefficients in rows / values[t * slots_per_target ...] (unordered),
+ * n_iter[t] sweeps run, converged[t] = 1 when the duality gap fell below tol * y.y.  slots_per_target = max(1, min(topK, n_items - 1)), n_items - 1 for topK = -1. */
+int mi355rec_slimen_get(mi355rec_slimen_t h, int32_t *counts, int32_t *n_iter, int32_t *converged, int32_t *rows, float *values,
+                        int32_t slots_per_target);
+int mi355rec_slimen_get_stats(mi355rec_slimen_t h, mi355rec_stats *stats);
+/* Counters of the last fit: accepted coordinate changes (= rows of G streamed), sweeps, block steps (windows of draws), duality-gap
+ * tests; h_in_lds = 1 when H was kept in LDS; gram_ms = device time of the Gram build of the create call. */
+int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, int64_t *sweeps, int64_t *steps, int64_t *gap_tests,
+                             int32_t *h_in_lds, double *gram_ms);
+void mi355rec_slimen_destroy(mi355rec_slimen_t h);
+
+/* ------------------------------------------------------------------------------------------------------
  * Scoring + ranking of factor models  (Base/BaseMatrixFactorizationRecommender.py:38
  * _compute_item_score and the filter/rank half of Base/BaseRecommender.py:131 recommend)
  * ---------------------------------------------------------------------------------------------------- */

@@ -25,6 +25,7 @@ from .knn import _ItemKNNLogic, _UserKNNLogic
 from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
 from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin
 from .slim_bpr import _SLIMLogic
+from .slim_elasticnet import _SLIMElasticNetLogic
 
 
 def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender, BaseUserSimilarityMatrixRecommender,
@@ -39,6 +40,7 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         "MatrixFactorization_AsySVD_MI355X": (_AsySVDLogic,) + mf,
         "IALSRecommender": (_IALSLogic,) + mf,
         "SLIM_BPR_MI355X": (_SLIMLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping),
+        "SLIMElasticNetRecommender": (_SLIMElasticNetLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "ItemKNNCFRecommender": (_ItemKNNLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "UserKNNCFRecommender": (_UserKNNLogic,) + sim_score + (BaseUserSimilarityMatrixRecommender,),
         "P3alphaRecommender": (_P3alphaLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
