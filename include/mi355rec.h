@@ -452,6 +452,47 @@ int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, 
 int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Holdout evaluation  (Base/Evaluation/Evaluator.py:225-275 evaluateRecommender, :294-374 _compute_metrics_on_recommendation_list,
+ * :404-450 EvaluatorHoldout._run_evaluation_on_selected_users; the metric functions of Base/Evaluation/metrics.py)
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_eval *mi355rec_eval_t;
+
+/* Per-user values of every cutoff, in this order (fp64; the float32 metrics hold their exact float32 value):
+ * roc_auc (metrics.py:102-118), precision (:136-144), precision_recall_min_denominator (:147-155), recall (:159-164),
+ * average_precision (:65-74), rr (:167-175), ndcg (:180-209), hits (Evaluator.py:339 HIT_RATE), arhr (:122-133), the Novelty sum
+ * (:562-572), the AveragePopularity mean (:614-621), and 1 when the list is not empty (Coverage_User, :361-362). */
+#define MI355REC_EVAL_VALUES 12
+
+/* URM_test AS PASSED (Evaluator.py:171, 279-291) as CSR with its stored values (the relevance of ndcg); rows need not be sorted.
+ * Lists are min(max(cutoffs), n_items) wide; the ideal DCG of every user (all of its test ratings, metrics.py:194) is computed
+ * here.  log_table = np.log(np.arange(log_len, dtype=np.float32) + 2) (metrics.py:208), log_len >= max(list width, longest
+ * test row).  Cutoffs must be distinct. */
+int mi355rec_eval_create(mi355rec_eval_t *out, int32_t n_users, int32_t n_items, const int32_t *test_indptr,
+                         const int32_t *test_indices, const double *test_relevance, const int32_t *cutoffs, int32_t n_cutoffs,
+                         const float *log_table, int32_t log_len);
+/* Starts an evaluation: per-item Novelty terms -log2(pop / n_interactions) / n_items (0 where pop == 0) and AveragePopularity terms
+ * pop / max(pop) (metrics.py:552-559, 601-611; pop = column counts of the recommender's URM_train), and the user ids of the whole
+ * evaluation, uploaded once.  Zeroes the accumulators. */
+int mi355rec_eval_begin(mi355rec_eval_t h, const double *novelty_term, const double *popularity_term, const int32_t *user_ids,
+                        int32_t n_eval);
+/* Evaluation positions [first, first + n): ranked[(row) * width ...] host lists, -1 padded at the end (Evaluator.py:436-442). */
+int mi355rec_eval_add_lists(mi355rec_eval_t h, int32_t first, int32_t n, const int32_t *ranked);
+/* The same users scored and ranked by a device scorer (as mi355rec_scorer_recommend / mi355rec_spscorer_recommend with
+ * cutoff = the list width); the lists never leave the device.  Asynchronous: the metric kernel runs on the scorer's stream. */
+int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                             const uint8_t *item_allowed);
+int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                               const uint8_t *item_allowed);
+/* sums[c * MI355REC_EVAL_VALUES + v]: value v summed over the evaluated users in a fixed order (the last one is the covered-user
+ * count); item_counts[c * n_items + i]: times item i was recommended within cutoff c (the recommended_counter of
+ * metrics.py:284-286, 762-769). */
+int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts);
+/* out[(p * n_cutoffs + c) * MI355REC_EVAL_VALUES + v]: the per-user values of the last evaluation, p = position of the user. */
+int mi355rec_eval_get_per_user(mi355rec_eval_t h, double *out);
+void mi355rec_eval_destroy(mi355rec_eval_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,14 @@ SIGNATURES = {
     "mi355rec_spscorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mi355rec_spscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_spscorer_destroy": (None, [_vp]),
+    "mi355rec_eval_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
+    "mi355rec_eval_begin": (C.c_int, [_vp, _vp, _vp, _vp, _i32]),
+    "mi355rec_eval_add_lists": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "mi355rec_eval_add_scorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_spscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_finish": (C.c_int, [_vp, _vp, _vp]),
+    "mi355rec_eval_get_per_user": (C.c_int, [_vp, _vp]),
+    "mi355rec_eval_destroy": (None, [_vp]),
 }
 
 _lib = None

@@ -17,6 +17,7 @@
 //                      one segmented radix sort (rocPRIM, stable: ties keep the lower item id, like the in-LDS path) orders every
 //                      row, the first `cutoff` finite entries are the ranking.
 #include "common.h"
+#include "score.h"
 #include "topk.cuh"
 
 #include <rocprim/rocprim.hpp>
@@ -278,6 +279,7 @@ struct WideRanker {
             capacity = total;
         }
         if (offsets_n < n || offsets_items != n_items) {
+            MI_HIP(hipStreamSynchronize(s));       // (earlier blocks on this stream may still read the old offsets)
             std::vector<int> host((size_t)n + 1);
             for (int b = 0; b <= n; ++b) host[b] = (int)((size_t)b * n_items);
             offsets.alloc((size_t)n + 1);
@@ -290,7 +292,10 @@ struct WideRanker {
         size_t bytes = 0;
         MI_HIP(rocprim::segmented_radix_sort_pairs_desc(nullptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
                                                                      n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
-        if (tmp.count < bytes) tmp.alloc(bytes + 256);
+        if (tmp.count < bytes) {
+            MI_HIP(hipStreamSynchronize(s));
+            tmp.alloc(bytes + 256);
+        }
         bytes = tmp.count;
         MI_HIP(rocprim::segmented_radix_sort_pairs_desc(tmp.ptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
                                                                      n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
@@ -377,6 +382,52 @@ extern "C" int mi355rec_scorer_update(mi355rec_scorer_t h, const float *U, const
     });
 }
 
+namespace mi355rec {
+// The score + rank half of mi355rec_scorer_recommend: enqueued on the scorer's stream, user ids and the item mask already in
+// device memory; the ranked lists stay in h->ranked.  Buffers only grow after the stream has drained (a caller that does not
+// synchronise between blocks -- the holdout evaluator -- may still have kernels reading the old ones).
+Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                       bool keep_scores) {
+    hipStream_t s = h->stream;
+    const bool wide = !fits_lds_rank(h->n_items, cutoff);
+    if (h->ranked.count < (size_t)n * cutoff || h->scores.count < (size_t)n * h->n_items ||
+        (wide && h->wide.capacity < (size_t)n * h->n_items)) {
+        MI_HIP(hipStreamSynchronize(s));
+        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
+        if (h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
+    }
+    h->call_timer.start(s);
+    ScoreParams sp{};
+    sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
+    sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
+    sp.users = users; sp.n_batch = n; sp.scores = h->scores.ptr;
+    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->gemm_timer.t0,
+                          h->gemm_timer.t1, 0, sp);
+    if (!wide) {
+        RankParams rp{};
+        rp.n_items = h->n_items; rp.n_pad = (h->n_items + 3) & ~3; rp.cutoff = cutoff;
+        rp.remove_seen = remove_seen;
+        rp.users = users; rp.seen_ptr = h->seen_ptr.ptr; rp.seen_idx = h->seen_idx.ptr;
+        rp.allowed = allowed;
+        rp.scores = h->scores.ptr; rp.ranked = h->ranked.ptr; rp.write_back = keep_scores;
+        const size_t lds = (size_t)rp.n_pad * 4 + (size_t)AUX_WORDS * 4;
+        auto k = score_rank_kernel<1024>;
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(n), dim3(1024), lds, s, rp);
+    } else {
+        h->wide.rank(s, h->scores.ptr, n, h->n_items, cutoff, users, h->seen_ptr.ptr, h->seen_idx.ptr, allowed, remove_seen,
+                     h->ranked.ptr);
+    }
+    MI_HIP(hipGetLastError());
+    h->call_timer.stop(s);
+    return Ranking{h->ranked.ptr, s};
+}
+
+void scorer_info(mi355rec_scorer_t h, int *n_users, int *n_items, hipStream_t *stream) {
+    *n_users = h->n_users; *n_items = h->n_items; *stream = h->stream;
+}
+}  // namespace mi355rec
+
 extern "C" int mi355rec_scorer_recommend(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                          int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
     return guarded([&] {
@@ -389,34 +440,9 @@ extern "C" int mi355rec_scorer_recommend(mi355rec_scorer_t h, const int32_t *use
         ensure_device();
         hipStream_t s = h->stream;
         if (h->users.count < (size_t)n) h->users.alloc(n);
-        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
-        if (h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
         MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
         if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-        h->call_timer.start(s);
-        ScoreParams sp{};
-        sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
-        sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
-        sp.users = h->users.ptr; sp.n_batch = n; sp.scores = h->scores.ptr;
-        hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->gemm_timer.t0,
-                              h->gemm_timer.t1, 0, sp);
-        if (fits_lds_rank(h->n_items, cutoff)) {
-            RankParams rp{};
-            rp.n_items = h->n_items; rp.n_pad = (h->n_items + 3) & ~3; rp.cutoff = cutoff;
-            rp.remove_seen = remove_seen;
-            rp.users = h->users.ptr; rp.seen_ptr = h->seen_ptr.ptr; rp.seen_idx = h->seen_idx.ptr;
-            rp.allowed = item_allowed ? h->allowed.ptr : nullptr;
-            rp.scores = h->scores.ptr; rp.ranked = h->ranked.ptr; rp.write_back = scores != nullptr;
-            const size_t lds = (size_t)rp.n_pad * 4 + (size_t)AUX_WORDS * 4;
-            auto k = score_rank_kernel<1024>;
-            MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k, dim3(n), dim3(1024), lds, s, rp);
-        } else {
-            h->wide.rank(s, h->scores.ptr, n, h->n_items, cutoff, h->users.ptr, h->seen_ptr.ptr, h->seen_idx.ptr,
-                         item_allowed ? h->allowed.ptr : nullptr, remove_seen, h->ranked.ptr);
-        }
-        MI_HIP(hipGetLastError());
-        h->call_timer.stop(s);
+        scorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
         h->ranked.download(ranked, (size_t)n * cutoff, s);
         if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
         MI_HIP(hipStreamSynchronize(s));
@@ -575,6 +601,47 @@ extern "C" int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_user
     });
 }
 
+namespace mi355rec {
+// The score + rank half of mi355rec_spscorer_recommend (see scorer_enqueue).
+Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                         bool keep_scores) {
+    hipStream_t s = h->stream;
+    const bool in_lds = fits_lds_rank(h->n_out, cutoff);
+    const bool need_scores = keep_scores || !in_lds;
+    if (h->ranked.count < (size_t)n * cutoff || (need_scores && h->scores.count < (size_t)n * h->n_out) ||
+        (!in_lds && h->wide.capacity < (size_t)n * h->n_out)) {
+        MI_HIP(hipStreamSynchronize(s));
+        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
+        if (need_scores && h->scores.count < (size_t)n * h->n_out) h->scores.alloc((size_t)n * h->n_out);
+    }
+    SpScoreParams p{};
+    p.n_out = h->n_out; p.n_pad = (h->n_out + 3) & ~3; p.cutoff = cutoff;
+    p.remove_seen = remove_seen; p.write_back = keep_scores;
+    p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
+    p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
+    p.users = users; p.seen_ptr = h->seen_ptr.ptr; p.seen_idx = h->seen_idx.ptr;
+    p.allowed = allowed;
+    p.scores = h->scores.ptr; p.ranked = h->ranked.ptr;
+    if (in_lds) {
+        const size_t lds = (size_t)p.n_pad * 4 + (size_t)AUX_WORDS * 4;
+        auto k = spscore_kernel<1024>;
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipExtLaunchKernelGGL(k, dim3(n), dim3(1024), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
+    } else {
+        MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_out, s));
+        hipExtLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, h->timer.t0, h->timer.t1, 0, p);
+        h->wide.rank(s, h->scores.ptr, n, h->n_out, cutoff, users, h->seen_ptr.ptr, h->seen_idx.ptr, p.allowed, remove_seen,
+                     h->ranked.ptr);
+    }
+    MI_HIP(hipGetLastError());
+    return Ranking{h->ranked.ptr, s};
+}
+
+void spscorer_info(mi355rec_spscorer_t h, int *n_users, int *n_items, hipStream_t *stream) {
+    *n_users = h->n_users; *n_items = h->n_out; *stream = h->stream;
+}
+}  // namespace mi355rec
+
 extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                            int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
     return guarded([&] {
@@ -585,31 +652,9 @@ extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t 
         ensure_device();
         hipStream_t s = h->stream;
         if (h->users.count < (size_t)n) h->users.alloc(n);
-        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
-        const bool in_lds = fits_lds_rank(h->n_out, cutoff);
-        if ((scores || !in_lds) && h->scores.count < (size_t)n * h->n_out) h->scores.alloc((size_t)n * h->n_out);
         MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
         if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_out, hipMemcpyHostToDevice, s));
-        SpScoreParams p{};
-        p.n_out = h->n_out; p.n_pad = (h->n_out + 3) & ~3; p.cutoff = cutoff;
-        p.remove_seen = remove_seen; p.write_back = scores != nullptr;
-        p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
-        p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
-        p.users = h->users.ptr; p.seen_ptr = h->seen_ptr.ptr; p.seen_idx = h->seen_idx.ptr;
-        p.allowed = item_allowed ? h->allowed.ptr : nullptr;
-        p.scores = h->scores.ptr; p.ranked = h->ranked.ptr;
-        if (in_lds) {
-            const size_t lds = (size_t)p.n_pad * 4 + (size_t)AUX_WORDS * 4;
-            auto k = spscore_kernel<1024>;
-            MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipExtLaunchKernelGGL(k, dim3(n), dim3(1024), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
-        } else {
-            MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_out, s));
-            hipExtLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, h->timer.t0, h->timer.t1, 0, p);
-            h->wide.rank(s, h->scores.ptr, n, h->n_out, cutoff, h->users.ptr, h->seen_ptr.ptr, h->seen_idx.ptr, p.allowed, remove_seen,
-                         h->ranked.ptr);
-        }
-        MI_HIP(hipGetLastError());
+        spscorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
         h->ranked.download(ranked, (size_t)n * cutoff, s);
         if (scores) h->scores.download(scores, (size_t)n * h->n_out, s);
         MI_HIP(hipStreamSynchronize(s));

@@ -76,6 +76,22 @@ def _fingerprint(array):
     return (np.asarray(array).shape, a[::step][:256].tobytes(), a[-1].tobytes())
 
 
+def allowed_items(recommender, items_to_compute=None, remove_top_pop_flag=False, remove_custom_items_flag=False):
+    """The item mask of recommend()'s filters (BaseRecommender.py:131-175: items outside `items_to_compute`, the top-popular and the
+    custom ignored items are dropped) as uint8, 0 = excluded; None when no filter applies."""
+    if items_to_compute is None and not remove_top_pop_flag and not remove_custom_items_flag:
+        return None
+    n_items = recommender.n_items
+    allowed = np.zeros(n_items, np.uint8) if items_to_compute is not None else np.ones(n_items, np.uint8)
+    if items_to_compute is not None:
+        allowed[np.asarray(items_to_compute)] = 1
+    if remove_top_pop_flag:
+        allowed[recommender.filterTopPop_ItemsID] = 0
+    if remove_custom_items_flag:
+        allowed[recommender.items_to_ignore_ID] = 0
+    return allowed
+
+
 class GpuScoringMixin:
     """recommend() of BaseRecommender (same signature, same return values) served by MI355XScorer.  The scorer is
     (re)built lazily from the host attributes USER_factors / ITEM_factors[/biases] and URM_train, so it follows
@@ -123,15 +139,7 @@ class GpuScoringMixin:
         users = np.atleast_1d(user_id_array)
         if cutoff is None:
             cutoff = self.URM_train.shape[1] - 1
-        allowed = None
-        if items_to_compute is not None or remove_top_pop_flag or remove_custom_items_flag:
-            allowed = np.zeros(self.n_items, np.uint8) if items_to_compute is not None else np.ones(self.n_items, np.uint8)
-            if items_to_compute is not None:
-                allowed[np.asarray(items_to_compute)] = 1
-            if remove_top_pop_flag:
-                allowed[self.filterTopPop_ItemsID] = 0
-            if remove_custom_items_flag:
-                allowed[self.items_to_ignore_ID] = 0
+        allowed = allowed_items(self, items_to_compute, remove_top_pop_flag, remove_custom_items_flag)
         scorer = self._get_scorer()
         assert scorer.n_users > np.max(users), \
             "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
@@ -214,15 +222,7 @@ class GpuSimilarityScoringMixin:
         users = np.atleast_1d(user_id_array)
         if cutoff is None:
             cutoff = self.URM_train.shape[1] - 1
-        allowed = None
-        if items_to_compute is not None or remove_top_pop_flag or remove_custom_items_flag:
-            allowed = np.zeros(self.n_items, np.uint8) if items_to_compute is not None else np.ones(self.n_items, np.uint8)
-            if items_to_compute is not None:
-                allowed[np.asarray(items_to_compute)] = 1
-            if remove_top_pop_flag:
-                allowed[self.filterTopPop_ItemsID] = 0
-            if remove_custom_items_flag:
-                allowed[self.items_to_ignore_ID] = 0
+        allowed = allowed_items(self, items_to_compute, remove_top_pop_flag, remove_custom_items_flag)
         ranked, scores = self._get_sparse_scorer().recommend(users, cutoff, remove_seen_flag, allowed, return_scores)
         # (-1 pads rows whose user has fewer than `cutoff` admissible items: rare -- one C-level tolist() otherwise, a tenth of the
         # per-row masks' time on blocks of 1000 users)
