@@ -417,6 +417,36 @@ int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, int64_t *swe
 void mi355rec_slimen_destroy(mi355rec_slimen_t h);
 
 /* ------------------------------------------------------------------------------------------------------
+ * PureSVD  (MatrixFactorization/PureSVDRecommender.py:34-47: sklearn's randomized_svd of URM_train) -- the device steps of the
+ * randomized SVD; the loop and the r x r factorisations (Cholesky, eigh) run on the host
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_svd *mi355rec_svd_t;
+
+/* URM_train (n_users x n_items) in both layouts, CSR and CSC, float32 values, indices inside the matrix; r = width of the two
+ * resident blocks, side 0 (n_users x r) and side 1 (n_items x r), float32 row-major, zero after create.  r < 1, pointers that
+ * decrease and indices outside the matrix are MI355REC_E_INVALID before the device is touched. */
+int mi355rec_svd_create(mi355rec_svd_t *out, int32_t n_users, int32_t n_items, int32_t r, const int32_t *row_ptr, const int32_t *row_idx,
+                        const float *row_val, const int32_t *col_ptr, const int32_t *col_idx, const float *col_val);
+/* Upload / download of the block of a side (rows_of(side) x r floats). */
+int mi355rec_svd_set_block(mi355rec_svd_t h, int32_t side, const float *X);
+int mi355rec_svd_get_block(mi355rec_svd_t h, int32_t side, float *X);
+/* dst_side 0: block[0] = URM . block[1];  dst_side 1: block[1] = URM^T . block[0].  Every output row is summed in a fixed order. */
+int mi355rec_svd_product(mi355rec_svd_t h, int32_t dst_side);
+/* G (r x r float64, row-major) = block[side]^T block[side], accumulated in float64. */
+int mi355rec_svd_gram(mi355rec_svd_t h, int32_t side, double *G);
+/* block[side] <- block[side] . T for T (r x r float32, row-major). */
+int mi355rec_svd_apply(mi355rec_svd_t h, int32_t side, const float *T);
+/* Timing of the last product (algorithmic_bytes = nnz (4 r + 8)). */
+int mi355rec_svd_get_stats(mi355rec_svd_t h, mi355rec_stats *stats);
+/* Totals since create: device milliseconds of the products, Gram builds and applies; kernel launches; calls of the entry points
+ * above; bytes uploaded by create (the URM and its piece tables); host -> device and device -> host bytes since;
+ * all_ones = 1 when the value stream is skipped. */
+int mi355rec_svd_fit_info(mi355rec_svd_t h, double *product_ms, double *gram_ms, double *apply_ms, int64_t *launches, int64_t *calls,
+                          int64_t *create_bytes, int64_t *h2d_bytes, int64_t *d2h_bytes, int32_t *all_ones);
+void mi355rec_svd_destroy(mi355rec_svd_t h);
+
+/* ------------------------------------------------------------------------------------------------------
  * Scoring + ranking of factor models  (Base/BaseMatrixFactorizationRecommender.py:38
  * _compute_item_score and the filter/rank half of Base/BaseRecommender.py:131 recommend)
  * ---------------------------------------------------------------------------------------------------- */

@@ -17,6 +17,9 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
                        bool keep_scores);
 Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                          bool keep_scores);
+// C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's
+// f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
+void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);
 void scorer_info(mi355rec_scorer_t h, int *n_users, int *n_items, hipStream_t *stream);
 void spscorer_info(mi355rec_spscorer_t h, int *n_users, int *n_items, hipStream_t *stream);
 

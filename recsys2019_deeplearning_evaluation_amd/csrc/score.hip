@@ -383,6 +383,16 @@ extern "C" int mi355rec_scorer_update(mi355rec_scorer_t h, const float *U, const
 }
 
 namespace mi355rec {
+void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s) {
+    if (n <= 0 || m <= 0) return;
+    ScoreParams sp{};
+    sp.n_users = n; sp.n_items = m; sp.k = k; sp.use_bias = 0;
+    sp.U = A; sp.V = Bt;
+    sp.users = rows; sp.n_batch = n; sp.scores = C;
+    hipLaunchKernelGGL(score_gemm_kernel, dim3(div_up(m, TN), div_up(n, TM)), dim3(256), 0, s, sp);
+    MI_HIP(hipGetLastError());
+}
+
 // The score + rank half of mi355rec_scorer_recommend: enqueued on the scorer's stream, user ids and the item mask already in
 // device memory; the ranked lists stay in h->ranked.  Buffers only grow after the stream has drained (a caller that does not
 // synchronise between blocks -- the holdout evaluator -- may still have kernels reading the old ones).

@@ -23,6 +23,7 @@ from .graph_based import _P3alphaLogic, _RP3betaLogic
 from .ials import _IALSLogic
 from .knn import _ItemKNNLogic, _UserKNNLogic
 from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
+from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
 from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin
 from .slim_bpr import _SLIMLogic
 from .slim_elasticnet import _SLIMElasticNetLogic
@@ -41,6 +42,8 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         "IALSRecommender": (_IALSLogic,) + mf,
         "SLIM_BPR_MI355X": (_SLIMLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping),
         "SLIMElasticNetRecommender": (_SLIMElasticNetLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
+        "PureSVDRecommender": (_PureSVDLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
+        "PureSVDItemRecommender": (_PureSVDItemLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "ItemKNNCFRecommender": (_ItemKNNLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "UserKNNCFRecommender": (_UserKNNLogic,) + sim_score + (BaseUserSimilarityMatrixRecommender,),
         "P3alphaRecommender": (_P3alphaLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
