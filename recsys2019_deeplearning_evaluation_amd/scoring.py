@@ -202,6 +202,13 @@ class GpuSimilarityScoringMixin:
     _sp_scorer = None
     _sp_scorer_src = None
 
+    def invalidate_scorer(self):
+        """Forget the device copy of the model (see GpuScoringMixin.invalidate_scorer): the next recommend() uploads it again."""
+        self._sp_scorer_src = None
+        if self._sp_scorer is not None:
+            self._sp_scorer.close()
+            self._sp_scorer = None
+
     def _get_sparse_scorer(self):
         # strong references + identity (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of
         # the first, freed matrix can be handed to its successor, so an id() key would score with stale weights)

@@ -6,6 +6,7 @@ import pytest
 from recsys2019_deeplearning_evaluation_amd import MI355XScorer, MatrixFactorization_BPR_MI355X
 from recsys2019_deeplearning_evaluation_amd import recommender_base as RB
 from recsys2019_deeplearning_evaluation_amd.synthetic import named_urm
+from ranking_cases import exact_ranking, exact_rankings
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +39,12 @@ def _check_ranking(ranked_row, score_row, cutoff, tol):
     assert (np.diff(score_row[got]) <= tol).all()                  # descending
 
 
+def _check_self_consistent(ranked, scores):
+    """No tolerance: the list is the exact ranking (value descending, ties towards the lower id, -1 padded) of the float32 scores
+    the same call returned (tests/ranking_cases.py)."""
+    np.testing.assert_array_equal(ranked, exact_rankings(scores, ranked.shape[1]))
+
+
 @pytest.mark.parametrize("k", [1, 7, 64, 128, 200])
 @pytest.mark.parametrize("use_bias", [False, True])
 def test_scores_and_ranking_match_host(gpu, k, use_bias):
@@ -54,6 +61,7 @@ def test_scores_and_ranking_match_host(gpu, k, use_bias):
     assert np.abs(scores[np.isfinite(want)] - want[np.isfinite(want)]).max() < 1e-5 * scale
     for r in range(len(users)):
         _check_ranking(ranked[r], want[r], 25, 1e-5 * scale)
+    _check_self_consistent(ranked, scores)
     st = sc.stats()
     assert st["algorithmic_flops"] == 2.0 * len(users) * X.shape[1] * k
     sc.close()
@@ -116,6 +124,7 @@ def test_similarity_model_scoring_matches_host(gpu, user_based):
     assert np.abs(dev_scores[fin] - host_scores[fin]).max() < 1e-5 * scale
     for r in range(len(users)):
         _check_ranking(np.array(dev_lists[r] + [-1] * (15 - len(dev_lists[r]))), host_scores[r].astype(np.float64), 15, 1e-5 * scale)
+        assert dev_lists[r] + [-1] * (15 - len(dev_lists[r])) == exact_ranking(dev_scores[r], 15).tolist()
     allowed_items = np.arange(0, X.shape[1], 3)
     only = rec.recommend(users[:5], cutoff=10, items_to_compute=allowed_items)
     assert all(set(l) <= set(allowed_items.tolist()) for l in only)
@@ -138,8 +147,9 @@ def test_large_catalogues_and_full_rankings_stay_on_the_device(gpu):
     for cutoff in (10, 5000, X.shape[1] - 1):                    # in-LDS selection impossible in all three cases (40 000 items)
         ranked, scores = sc.recommend(users, cutoff, remove_seen=True, return_scores=True)
         assert np.abs(scores[np.isfinite(want)] - want[np.isfinite(want)]).max() < 1e-5 * scale
-        for r in range(0, len(users), 7):
+        for r in range(len(users)):
             _check_ranking(ranked[r], want[r], cutoff, 1e-5 * scale)
+        _check_self_consistent(ranked, scores)
     sc.close()
     # a small catalogue with a cutoff above the in-LDS selection limit (the Evaluator never asks for it, recommend(user) does)
     Xs = named_urm("ml1m", "binary", scale=0.3)
@@ -159,8 +169,9 @@ def test_large_catalogues_and_full_rankings_stay_on_the_device(gpu):
         host[r, X.indices[X.indptr[u]:X.indptr[u + 1]]] = -np.inf
     fin = np.isfinite(host)
     assert (np.isfinite(scores) == fin).all() and np.abs(scores[fin] - host[fin]).max() < 1e-5 * max(np.abs(host[fin]).max(), 1e-30)
-    for r in range(0, len(users), 5):
+    for r in range(len(users)):
         _check_ranking(ranked[r], host[r], 20, 1e-5 * max(np.abs(host[fin]).max(), 1e-30))
+    _check_self_consistent(ranked, scores)
     sp.close()
 
 
@@ -230,4 +241,48 @@ def test_reference_generated_fixture(gpu, tag):
         clear[1:] &= (ws[:-1] - ws[1:]) > 2 * tol
         clear[:-1] &= (ws[:-1] - ws[1:]) > 2 * tol
         np.testing.assert_array_equal(got[clear], want[clear])
+    _check_self_consistent(ranked, scores)
     sc.close()
+
+
+def _ulp32(x):
+    return np.spacing(np.abs(x).astype(np.float32)).astype(np.float64)
+
+
+@pytest.mark.parametrize("k", [2, 3, 5, 31, 32, 33, 63, 65, 255])
+def test_gemm_edge_shapes_within_the_dot_product_bound(gpu, k):
+    """Factor counts around the K chunk (32) and the 16-byte loads (k % 4), catalogues and batches around the 128 x 128 tile, against
+    the float64 product with a PER-CELL bound that is derived, not measured: a length-k float32 dot product in any order is within
+    gamma_k * sum_j |U_uj V_ij| of the exact one, gamma_k = k 2^-24 / (1 - k 2^-24) (Higham, Accuracy and Stability of Numerical
+    Algorithms, section 3.1); with biases one float32 ulp more for each of the three additions (item bias + global bias, + dot
+    product, + user bias), taken at the magnitude the partial result can have."""
+    from ranking_cases import random_seen
+    rng = np.random.default_rng(k)
+    n_users = 140
+    gamma = k * 2.0 ** -24 / (1 - k * 2.0 ** -24)
+    for n_items in (1, 127, 128, 129):
+        U = rng.normal(size=(n_users, k)).astype(np.float32); V = rng.normal(size=(n_items, k)).astype(np.float32)
+        bu, bi = rng.normal(size=n_users).astype(np.float32), rng.normal(size=n_items).astype(np.float32)
+        mu = np.float32(0.7)
+        X = random_seen(n_users, n_items, 1, rng)
+        for use_bias in (False, True):
+            sc = MI355XScorer(U, V, X, *((bu, bi, mu) if use_bias else ()))
+            for batch in (1, 127, 128, 129):
+                users = rng.permutation(n_users)[:batch]
+                cutoff = max(1, n_items // 2)
+                ranked, scores = sc.recommend(users, cutoff, remove_seen=False, return_scores=True)
+                Ud, Vd = U[users].astype(np.float64), V.astype(np.float64)
+                want = Ud @ Vd.T
+                bound = gamma * (np.abs(Ud) @ np.abs(Vd).T)
+                if use_bias:
+                    item_term = bi.astype(np.float64) + float(mu)
+                    bound = bound + _ulp32(item_term)
+                    want = want + item_term
+                    bound = bound + _ulp32(np.abs(want) + bound)
+                    want = want + bu[users].astype(np.float64)[:, None]
+                    bound = bound + _ulp32(np.abs(want) + bound)
+                excess = np.abs(scores.astype(np.float64) - want) - bound
+                at = np.unravel_index(np.argmax(excess), excess.shape)
+                assert excess[at] <= 0, (n_items, use_bias, batch, at, float(scores[at]), float(want[at]), float(bound[at]))
+                _check_self_consistent(ranked, scores)
+            sc.close()
