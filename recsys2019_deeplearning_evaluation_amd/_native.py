@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (MI355REC_LIB: another build of the same library, for measurements of compile-time variants -- scripts/sim_depth_sweep.sh)
+# (MI355REC_LIB: another build of the same library, for measurements of compile-time variants)
 LIB_PATH = os.environ.get("MI355REC_LIB") or os.path.join(_HERE, "libmi355rec.so")
 
 E_INVALID, E_HIP, E_NO_DEVICE, E_UNSUPPORTED, E_NUMERIC = -1, -2, -3, -4, -5
@@ -209,6 +209,42 @@ def check(rc):
     if rc == E_NUMERIC:
         raise FloatingPointError(msg)
     raise NativeLibraryError(msg)
+
+
+class Handle:
+    """Base of every wrapper of a native handle type: `_PREFIX` names its entry points ("mi355rec_ials" -> mi355rec_ials_create,
+    mi355rec_ials_<name>, mi355rec_ials_get_stats, mi355rec_ials_destroy).  `_h` is the handle (a c_void_p) while the object is
+    open and None before a successful _create and after close()."""
+    _PREFIX = None
+    _h = None
+
+    def _create(self, *args, entry="create"):
+        self._lib = load()
+        h = C.c_void_p()
+        check(getattr(self._lib, "%s_%s" % (self._PREFIX, entry))(C.byref(h), *args))
+        self._h = h
+
+    def _call(self, name, *args):
+        if not self._h:
+            raise ValueError("%s is closed" % type(self).__name__)
+        check(getattr(self._lib, "%s_%s" % (self._PREFIX, name))(self._h, *args))
+
+    def stats(self):
+        """The library's figures of the last call on this handle, as a dict."""
+        st = Stats()
+        self._call("get_stats", C.byref(st))
+        return st.as_dict()
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            getattr(self._lib, self._PREFIX + "_destroy")(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def ptr(array):

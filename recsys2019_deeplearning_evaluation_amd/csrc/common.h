@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -128,28 +129,9 @@ hipEvent_t pooled_event();
 void pooled_event_return(hipEvent_t e);
 
 // ---- event-pair timer on a stream -------------------------------------------------------------------
+// The events belong to the Handle below, which creates them (or takes them from the pool) and gives them up.
 struct StreamTimer {
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool pooled = false;
-    void init() {
-        MI_HIP(hipEventCreate(&t0));
-        MI_HIP(hipEventCreate(&t1));
-    }
-    void init_pooled() {
-        t0 = pooled_event();
-        t1 = pooled_event();
-        pooled = true;
-    }
-    void destroy() {
-        if (pooled) {
-            if (t0) pooled_event_return(t0);
-            if (t1) pooled_event_return(t1);
-        } else {
-            if (t0) (void)hipEventDestroy(t0);
-            if (t1) (void)hipEventDestroy(t1);
-        }
-        t0 = t1 = nullptr;
-    }
     void start(hipStream_t s) { MI_HIP(hipEventRecord(t0, s)); }
     void stop(hipStream_t s) { MI_HIP(hipEventRecord(t1, s)); }
     // valid after the stream has been synchronised past stop()
@@ -200,5 +182,74 @@ struct DispatchTimers {
 };
 
 static inline int div_up(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
+
+// ---- what every handle struct (struct mi355rec_*) is built on ---------------------------------------------------------------------
+// A handle's streams, its event timers and the stats of its last call, with the one teardown all handles share.  A handle struct
+// derives from Handle, opens it in its create function and ends it in a one-line destructor:
+//     ~mi355rec_x() { shutdown(); }        or        ~mi355rec_x() { shutdown([&] { /* graphs, events of its own */ }); }
+// The destructor is what makes the order below hold: it runs BEFORE the struct's DeviceBuffer members are destroyed (Handle's own
+// destructor would run after them), and it also runs when a create function fails half-way, through its unique_ptr: nothing leaks.
+enum class StreamFrom { Created, Pool };   // Pool: stream and timer events come from, and go back to, the per-process pool above
+
+struct Handle {
+    hipStream_t stream = nullptr;
+    hipStream_t side = nullptr;         // second stream of the handles that overlap two chains of launches (open_side)
+    StreamTimer timer, call_timer;      // open(n_timers): 1 = `timer` only, 2 = both
+    DispatchTimers dispatch_timers;     // grown on demand by the handles that time single dispatches
+    mi355rec_stats stats{};             // of the last call, read by handle_get_stats()
+
+    void open(int n_timers, StreamFrom from = StreamFrom::Created);
+    void open_side();
+    // Teardown, in the order that is a correctness rule:
+    //   1. drain the streams (nothing of this handle runs any more);
+    //      then `own`: what the handle itself holds on those streams -- graphs, events -- goes while they still exist;
+    //   2. give up the timer events;
+    //   3. ReleaseScope::forget the streams: the block returns of step 5 must not synchronise a stream that is gone, and need
+    //      not synchronise a drained one once per buffer;
+    //   4. destroy the streams, or hand them back to the pool;
+    //   5. only then, after the destructor that called this, the DeviceBuffer members hand their blocks back.
+    // Idempotent; never throws.
+    template <class F>
+    void shutdown(F &&own) noexcept {
+        drain();
+        own();
+        release_streams();
+    }
+    void shutdown() noexcept { shutdown([] {}); }
+
+    Handle() = default;
+    Handle(const Handle &) = delete;
+    Handle &operator=(const Handle &) = delete;
+
+private:
+    bool pooled_ = false;
+    void drain() noexcept;              // step 1
+    void release_streams() noexcept;    // steps 2 - 4
+};
+
+// ensure_device() + the handle struct + its stream and timers: the start of a create function whose argument checks are done
+template <class H>
+std::unique_ptr<H> open_handle(int n_timers, StreamFrom from = StreamFrom::Created) {
+    ensure_device();
+    std::unique_ptr<H> h(new H());
+    h->open(n_timers, from);
+    return h;
+}
+
+// the bodies of mi355rec_<type>_get_stats and mi355rec_<type>_destroy
+template <class H>
+int handle_get_stats(const H *h, mi355rec_stats *stats) {
+    return guarded([&] {
+        MI_REQUIRE(h && stats, "NULL argument");
+        *stats = h->stats;
+    });
+}
+
+template <class H>
+void handle_destroy(H *h) {
+    if (!h) return;
+    ReleaseScope scope(h->stream, h->side);     // the buffers' block returns wait for this handle's streams only (all drained by then)
+    delete h;
+}
 
 }  // namespace mi355rec

@@ -217,6 +217,44 @@ void pooled_event_return(hipEvent_t e) {
     else (void)hipEventDestroy(e);
 }
 
+// ---- Handle (common.h) ------------------------------------------------------------------------------------------------------------
+void Handle::open(int n_timers, StreamFrom from) {
+    pooled_ = from == StreamFrom::Pool;
+    if (pooled_) stream = pooled_stream();
+    else MI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    StreamTimer *timers[2] = {&timer, &call_timer};
+    for (int i = 0; i < n_timers; ++i)
+        for (hipEvent_t *e : {&timers[i]->t0, &timers[i]->t1}) {
+            if (pooled_) *e = pooled_event();
+            else MI_HIP(hipEventCreate(e));
+        }
+}
+
+void Handle::open_side() {
+    if (!side) MI_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+}
+
+void Handle::drain() noexcept {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (side) (void)hipStreamSynchronize(side);
+}
+
+void Handle::release_streams() noexcept {
+    for (hipEvent_t *e : {&timer.t0, &timer.t1, &call_timer.t0, &call_timer.t1}) {
+        if (*e && pooled_) pooled_event_return(*e);
+        else if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+    dispatch_timers.destroy();
+    for (hipStream_t *s : {&side, &stream}) {
+        if (!*s) continue;
+        ReleaseScope::forget(*s);
+        if (pooled_ && s == &stream) pooled_stream_return(*s);
+        else (void)hipStreamDestroy(*s);
+        *s = nullptr;
+    }
+}
+
 }  // namespace mi355rec
 
 using namespace mi355rec;

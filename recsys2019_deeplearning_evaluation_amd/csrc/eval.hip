@@ -217,9 +217,8 @@ float host_pairwise(const float *a, long n) {
 
 using namespace mi355rec;
 
-struct mi355rec_eval {
+struct mi355rec_eval : Handle {
     int n_users = 0, n_items = 0, n_cut = 0, n_sorted = 0, width = 0, n_eval = 0;
-    hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;          // recorded after every metric launch, on whichever stream ran it
     std::vector<int> cut_host, sorted_host, users_host;
     std::vector<unsigned char> allowed_host;
@@ -230,10 +229,9 @@ struct mi355rec_eval {
     DeviceBuffer<unsigned char> allowed;
 
     ~mi355rec_eval() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
+        shutdown([&] {
+            if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); }
+        });
     }
 };
 
@@ -271,20 +269,18 @@ const unsigned char *device_mask(mi355rec_eval *h, const uint8_t *allowed) {
     return h->allowed.ptr;
 }
 
-template <class Handle, class Info, class Enqueue>
-void add_from_scorer(mi355rec_eval *h, Handle sc, int first, int n, int remove_seen, const uint8_t *allowed, Info info, Enqueue enqueue) {
+template <class Scorer, class Enqueue>
+void add_from_scorer(mi355rec_eval *h, Scorer *sc, int first, int n, int remove_seen, const uint8_t *allowed, Enqueue enqueue) {
     MI_REQUIRE(h && sc, "NULL argument");
     check_block(h, first, n);
-    int su = 0, si = 0;
-    hipStream_t ss = nullptr;
-    info(sc, &su, &si, &ss);
+    const int su = sc->n_users, si = sc->n_items;
     MI_REQUIRE(si == h->n_items, "the recommender scores %d items, URM_test has %d", si, h->n_items);
     for (int i = first; i < first + n; ++i)
         MI_REQUIRE(h->users_host[i] < su, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d",
                    su, h->users_host[i]);
     ensure_device();
     const unsigned char *mask = device_mask(h, allowed);
-    MI_HIP(hipStreamWaitEvent(ss, h->done, 0));         // (begin's zeroing, a lists-path block on the evaluator's stream)
+    MI_HIP(hipStreamWaitEvent(sc->stream, h->done, 0)); // (begin's zeroing, a lists-path block on the evaluator's stream)
     const Ranking r = enqueue(sc, h->users.ptr + first, n, h->width, remove_seen, mask, false);
     launch_metrics(h, r.stream, r.ranked, first, n);    // behind the ranking, on the scorer's stream: the next block's ranking
 }                                                       // cannot overwrite `ranked` before this kernel has read it
@@ -333,7 +329,7 @@ extern "C" int mi355rec_eval_create(mi355rec_eval_t *out, int32_t n_users, int32
             idcg[u] = host_pairwise(terms.data(), (long)terms.size());
         }
         ensure_device();
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        h->open(0);
         MI_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
         hipStream_t s = h->stream;
         h->cut.upload(h->cut_host.data(), n_cutoffs, s);
@@ -399,12 +395,12 @@ extern "C" int mi355rec_eval_add_lists(mi355rec_eval_t h, int32_t first, int32_t
 
 extern "C" int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                         const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, scorer_info, scorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, scorer_enqueue); });
 }
 
 extern "C" int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                           const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, spscorer_info, spscorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue); });
 }
 
 extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts) {
@@ -440,8 +436,4 @@ extern "C" int mi355rec_eval_get_per_user(mi355rec_eval_t h, double *out) {
     });
 }
 
-extern "C" void mi355rec_eval_destroy(mi355rec_eval_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_eval_destroy(mi355rec_eval_t h) { handle_destroy(h); }

@@ -697,13 +697,10 @@ __global__ void ials_scatter_kernel(const int *ptr, const int *idx, const float 
 
 using namespace mi355rec;
 
-struct mi355rec_ials {
+struct mi355rec_ials : Handle {
     int n_users = 0, n_items = 0, k = 0;
     double reg = 0;
     size_t nnz = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer call_timer;
-    DispatchTimers dispatch_timers;
     DeviceBuffer<int> u_ptr, u_idx, i_ptr, i_idx;
     DeviceBuffer<int4> items;
     DeviceBuffer<double> part_buf;
@@ -722,17 +719,10 @@ struct mi355rec_ials {
     std::vector<int> user_order, item_order;     // longest profile first
     std::vector<int> u_ptr_host, i_ptr_host;
     std::vector<int> staging;
-    mi355rec_stats stats{};
     double flops_acc = 0, bytes_acc = 0;
     long long rows_acc = 0, launches_acc = 0;
 
-    ~mi355rec_ials() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        call_timer.destroy();
-        dispatch_timers.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~mi355rec_ials() { shutdown(); }
 };
 
 namespace {
@@ -1068,14 +1058,14 @@ void begin_call(mi355rec_ials *h, int rows) {
     h->dispatch_timers.reset();
     h->flops_acc = h->bytes_acc = 0;
     h->rows_acc = h->launches_acc = 0;
-    h->call_timer.start(h->stream);
+    h->timer.start(h->stream);
 }
 
 void end_call(mi355rec_ials *h, bool sync) {
-    h->call_timer.stop(h->stream);
+    h->timer.stop(h->stream);
     if (!sync) return;
     MI_HIP(hipStreamSynchronize(h->stream));
-    h->stats.call_ms = h->call_timer.elapsed_ms();
+    h->stats.call_ms = h->timer.elapsed_ms();
     h->stats.kernel_ms = h->dispatch_timers.total_ms();
     h->stats.n_timed = h->dispatch_timers.used;
     h->stats.n_launches = h->launches_acc;
@@ -1104,8 +1094,7 @@ extern "C" int mi355rec_ials_create(mi355rec_ials_t *out, int32_t n_users, int32
         h->reg = reg;
         h->nnz = (size_t)indptr[n_users];
         MI_REQUIRE(h->nnz > 0, "URM has no interactions");
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->call_timer.init();
+        h->open(1);
         h->dispatch_timers.reserve(8);
         hipStream_t s = h->stream;
         const size_t nnz = h->nnz;
@@ -1200,7 +1189,7 @@ extern "C" int mi355rec_ials_sync(mi355rec_ials_t h) {
         MI_REQUIRE(h, "NULL handle");
         ensure_device();
         MI_HIP(hipStreamSynchronize(h->stream));
-        h->stats.call_ms = h->call_timer.elapsed_ms();
+        h->stats.call_ms = h->timer.elapsed_ms();
         h->stats.kernel_ms = h->dispatch_timers.total_ms();
         h->stats.n_timed = h->dispatch_timers.used;
         h->stats.n_launches = h->launches_acc;
@@ -1228,15 +1217,6 @@ extern "C" int mi355rec_ials_schedule_info(mi355rec_ials_t h, int32_t *n_split_r
     });
 }
 
-extern "C" int mi355rec_ials_get_stats(mi355rec_ials_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_ials_get_stats(mi355rec_ials_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
-extern "C" void mi355rec_ials_destroy(mi355rec_ials_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_ials_destroy(mi355rec_ials_t h) { handle_destroy(h); }

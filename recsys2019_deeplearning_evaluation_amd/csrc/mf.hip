@@ -53,14 +53,12 @@
 
 using namespace mi355rec;
 
-struct mi355rec_mf {
+struct mi355rec_mf : Handle {
     mi355rec_mf_config cfg{};
     int n_users = 0, n_items = 0, k = 0;
     int n_u_rows = 0;                 // rows of U: n_users, or n_items for AsySVD
     bool f64 = false;                 // storage / arithmetic type of factors and moments
     size_t nnz = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer timer;
     DeviceBuffer<int> indptr, indices, su, si, sj;
     DeviceBuffer<float> data, sr, stage;
     // T-typed arrays (float or double by `f64`), held as bytes
@@ -84,8 +82,6 @@ struct mi355rec_mf {
     long long batch_capacity = 0;    // mini-batches the task arrays can hold
     long long batches_done = 0;      // batches executed since create (device state mirrors this)
     long long last_call_samples = 0; // samples in the stream buffer after the last native call
-    mi355rec_stats stats{};
-    DispatchTimers dispatch_timers;
     int max_timed = 0;
     // exact multi-GPU mode: this rank's share of every mini-batch and the exchange slabs
     DeviceBuffer<unsigned char> shard_send, shard_recv;
@@ -101,14 +97,7 @@ struct mi355rec_mf {
         for (hipGraphExec_t g : epoch_graphs) (void)hipGraphExecDestroy(g);
         epoch_graphs.clear();
     }
-    ~mi355rec_mf() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        drop_graphs();
-        timer.destroy();
-        dispatch_timers.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~mi355rec_mf() { shutdown([&] { drop_graphs(); }); }
 };
 
 namespace {
@@ -701,8 +690,7 @@ extern "C" int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *
         h->f64 = cfg->precision == MI355REC_F64;
         h->nnz = (size_t)indptr[n_users];
         MI_REQUIRE(h->nnz > 0, "URM has no interactions");
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->timer.init();
+        h->open(1);
         hipStream_t s = h->stream;
         h->indptr.upload(indptr, (size_t)n_users + 1, s);
         h->indices.upload(indices, h->nnz, s);
@@ -878,15 +866,12 @@ extern "C" int mi355rec_mf_shard_end_epoch(mi355rec_mf_t h) {
 }
 
 // ---- replica-batched epochs: R independent models, one launch per mini-batch index ---------------------------------------------
-struct mi355rec_mf_group {
+struct mi355rec_mf_group : Handle {
     std::vector<mi355rec_mf *> members;      // not owned
     bool f64 = false;
     int algorithm = 0, klass = 0, tasks_per_batch = 0;
     bool plain_sgd = false;                 // every member runs sgd_mode "sgd"
     long long batches_per_epoch = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer timer;
-    DispatchTimers dispatch_timers;
     int max_timed = 0;
     DeviceBuffer<unsigned char> table;       // MfParams<T>[R]
     std::vector<unsigned char> host_table;
@@ -905,28 +890,20 @@ struct mi355rec_mf_group {
     std::vector<std::unique_ptr<SetB>> set_b;
     DeviceBuffer<unsigned char> table_b;
     DeviceBuffer<FastSchedParams> sched_table_b;
-    hipStream_t side = nullptr;
     hipEvent_t ahead_fork = nullptr, ahead_join = nullptr;
     hipEvent_t fork = nullptr;
     std::vector<hipEvent_t> join;
     hipGraphExec_t graph = nullptr;
     bool graph_failed = false;
-    mi355rec_stats stats{};
 
     ~mi355rec_mf_group() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (side) (void)hipStreamSynchronize(side);
-        if (ahead_fork) (void)hipEventDestroy(ahead_fork);
-        if (ahead_join) (void)hipEventDestroy(ahead_join);
-        ReleaseScope::forget(side);
-        if (side) (void)hipStreamDestroy(side);
-        if (graph) (void)hipGraphExecDestroy(graph);
-        timer.destroy();
-        dispatch_timers.destroy();
-        if (fork) (void)hipEventDestroy(fork);
-        for (auto e : join) (void)hipEventDestroy(e);
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
+        shutdown([&] {
+            if (ahead_fork) (void)hipEventDestroy(ahead_fork);
+            if (ahead_join) (void)hipEventDestroy(ahead_join);
+            if (graph) (void)hipGraphExecDestroy(graph);
+            if (fork) (void)hipEventDestroy(fork);
+            for (auto e : join) (void)hipEventDestroy(e);
+        });
     }
 };
 
@@ -1087,7 +1064,7 @@ void group_run_epochs_typed(mi355rec_mf_group *g, int n_epochs) {
         }
         if (fresh) {
             MI_HIP(hipStreamSynchronize(g->stream));
-            if (!g->side) MI_HIP(hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking));
+            g->open_side();
             if (!g->ahead_fork) MI_HIP(hipEventCreateWithFlags(&g->ahead_fork, hipEventDisableTiming));
             if (!g->ahead_join) MI_HIP(hipEventCreateWithFlags(&g->ahead_join, hipEventDisableTiming));
             g->set_b.clear();
@@ -1202,8 +1179,7 @@ extern "C" int mi355rec_mf_group_create(mi355rec_mf_group_t *out, const mi355rec
         }
         g->plain_sgd = true;
         for (const mi355rec_mf *h : g->members) g->plain_sgd = g->plain_sgd && h->cfg.sgd_mode == MI355REC_SGD;
-        MI_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        g->timer.init();
+        g->open(1);
         MI_HIP(hipEventCreateWithFlags(&g->fork, hipEventDisableTiming));
         g->join.resize(n_members, nullptr);
         for (auto &e : g->join) MI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1230,18 +1206,9 @@ extern "C" int mi355rec_mf_group_set_profiling(mi355rec_mf_group_t g, int32_t ma
     });
 }
 
-extern "C" int mi355rec_mf_group_get_stats(mi355rec_mf_group_t g, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(g && stats, "NULL argument");
-        *stats = g->stats;
-    });
-}
+extern "C" int mi355rec_mf_group_get_stats(mi355rec_mf_group_t g, mi355rec_stats *stats) { return handle_get_stats(g, stats); }
 
-extern "C" void mi355rec_mf_group_destroy(mi355rec_mf_group_t g) {
-    if (!g) return;
-    ReleaseScope scope(g->stream);
-    delete g;
-}
+extern "C" void mi355rec_mf_group_destroy(mi355rec_mf_group_t g) { handle_destroy(g); }
 
 extern "C" int mi355rec_mf_get_factors(mi355rec_mf_t h, float *U, float *V, float *bu, float *bi, float *mu) {
     return guarded([&] {
@@ -1297,15 +1264,7 @@ extern "C" int mi355rec_mf_get_phase_ticks(mi355rec_mf_t h, uint64_t *out, int64
     });
 }
 
-extern "C" int mi355rec_mf_get_stats(mi355rec_mf_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_mf_get_stats(mi355rec_mf_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
-extern "C" void mi355rec_mf_destroy(mi355rec_mf_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);       // (a group's launches on the group's stream have been waited for by the call that made them)
-    delete h;
-}
+// (a group's launches on the group's stream have been waited for by the call that made them)
+extern "C" void mi355rec_mf_destroy(mi355rec_mf_t h) { handle_destroy(h); }

@@ -1,8 +1,52 @@
-// score.h -- the "score + rank on the handle's stream" half of mi355rec_scorer_recommend / mi355rec_spscorer_recommend
-// (score.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists where these leave them.
+// score.h -- the two scorer handles and the "score + rank on the handle's stream" half of mi355rec_scorer_recommend /
+// mi355rec_spscorer_recommend (score.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists
+// where these leave them.
 #pragma once
 
 #include "common.h"
+
+namespace mi355rec {
+
+// ranking of score rows that stay in HBM (score.hip, "wide ranking")
+struct WideRanker {
+    DeviceBuffer<int> ids_in, ids_out, offsets;
+    DeviceBuffer<float> keys_out;
+    DeviceBuffer<unsigned char> tmp;
+    size_t capacity = 0;
+    int offsets_n = 0, offsets_items = 0;
+
+    // scores: [n][n_items] in HBM (unfiltered); ranked: [n][cutoff] on the device
+    void rank(hipStream_t s, float *scores, int n, int n_items, int cutoff, const int *users, const int *seen_ptr, const int *seen_idx,
+              const unsigned char *allowed, int remove_seen, int *ranked);
+};
+
+// what the two scorers share: mi355rec_*scorer_recommend and the evaluator's add_from_scorer are written against these members
+struct ScorerHandle : Handle {
+    WideRanker wide;
+    int n_users = 0, n_items = 0;       // rows that can be asked for, width of a score row
+    DeviceBuffer<int> seen_ptr, seen_idx, users, ranked;
+    DeviceBuffer<float> scores;
+    DeviceBuffer<unsigned char> allowed;
+};
+
+}  // namespace mi355rec
+
+struct mi355rec_scorer : mi355rec::ScorerHandle {    // `timer`: the GEMM dispatch; `call_timer`: GEMM + ranking
+    int k = 0, use_bias = 0;
+    float mu = 0.f;
+    mi355rec::DeviceBuffer<float> U, V, bu, bi;
+
+    ~mi355rec_scorer() { shutdown(); }
+};
+
+struct mi355rec_spscorer : mi355rec::ScorerHandle {  // `timer`: the scoring dispatch
+    int n_mid = 0;
+    mi355rec::DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx;
+    mi355rec::DeviceBuffer<float> a_val, b_val;
+    double nnz_a = 0, nnz_b = 0;
+
+    ~mi355rec_spscorer() { shutdown(); }
+};
 
 namespace mi355rec {
 
@@ -20,7 +64,5 @@ Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cut
 // C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's
 // f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
 void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);
-void scorer_info(mi355rec_scorer_t h, int *n_users, int *n_items, hipStream_t *stream);
-void spscorer_info(mi355rec_spscorer_t h, int *n_users, int *n_items, hipStream_t *stream);
 
 }  // namespace mi355rec

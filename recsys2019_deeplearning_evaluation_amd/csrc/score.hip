@@ -262,47 +262,42 @@ __global__ __launch_bounds__(256) void wide_emit_kernel(const float *sorted_scor
     }
 }
 
-struct WideRanker {
-    DeviceBuffer<int> ids_in, ids_out, offsets;
-    DeviceBuffer<float> keys_out;
-    DeviceBuffer<unsigned char> tmp;
-    size_t capacity = 0;
-    int offsets_n = 0, offsets_items = 0;
+}  // namespace
 
-    // scores: [n][n_items] in HBM (unfiltered); ranked: [n][cutoff] on the device
-    void rank(hipStream_t s, float *scores, int n, int n_items, int cutoff, const int *users, const int *seen_ptr, const int *seen_idx,
-              const unsigned char *allowed, int remove_seen, int *ranked) {
-        const size_t total = (size_t)n * n_items;
-        if (total >= (1ull << 31)) fail(MI355REC_E_UNSUPPORTED, "user block of %d x %d scores exceeds the segmented sort (2^31 cells): use smaller blocks", n, n_items);
-        if (capacity < total) {
-            ids_in.alloc(total); ids_out.alloc(total); keys_out.alloc(total);
-            capacity = total;
-        }
-        if (offsets_n < n || offsets_items != n_items) {
-            MI_HIP(hipStreamSynchronize(s));       // (earlier blocks on this stream may still read the old offsets)
-            std::vector<int> host((size_t)n + 1);
-            for (int b = 0; b <= n; ++b) host[b] = (int)((size_t)b * n_items);
-            offsets.alloc((size_t)n + 1);
-            MI_HIP(hipMemcpyAsync(offsets.ptr, host.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
-            MI_HIP(hipStreamSynchronize(s));
-            offsets_n = n; offsets_items = n_items;
-        }
-        hipLaunchKernelGGL(wide_filter_kernel, dim3(std::min(div_up(n_items, 256), 64), n), dim3(256), 0, s, scores, ids_in.ptr, n_items,
-                           users, seen_ptr, seen_idx, allowed, remove_seen);
-        size_t bytes = 0;
-        MI_HIP(rocprim::segmented_radix_sort_pairs_desc(nullptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
-                                                                     n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
-        if (tmp.count < bytes) {
-            MI_HIP(hipStreamSynchronize(s));
-            tmp.alloc(bytes + 256);
-        }
-        bytes = tmp.count;
-        MI_HIP(rocprim::segmented_radix_sort_pairs_desc(tmp.ptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
-                                                                     n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
-        hipLaunchKernelGGL(wide_emit_kernel, dim3(std::min(div_up(cutoff, 256), 64), n), dim3(256), 0, s, keys_out.ptr, ids_out.ptr, n_items,
-                           cutoff, ranked);
+void WideRanker::rank(hipStream_t s, float *scores, int n, int n_items, int cutoff, const int *users, const int *seen_ptr,
+                      const int *seen_idx, const unsigned char *allowed, int remove_seen, int *ranked) {
+    const size_t total = (size_t)n * n_items;
+    if (total >= (1ull << 31)) fail(MI355REC_E_UNSUPPORTED, "user block of %d x %d scores exceeds the segmented sort (2^31 cells): use smaller blocks", n, n_items);
+    if (capacity < total) {
+        ids_in.alloc(total); ids_out.alloc(total); keys_out.alloc(total);
+        capacity = total;
     }
-};
+    if (offsets_n < n || offsets_items != n_items) {
+        MI_HIP(hipStreamSynchronize(s));       // (earlier blocks on this stream may still read the old offsets)
+        std::vector<int> host((size_t)n + 1);
+        for (int b = 0; b <= n; ++b) host[b] = (int)((size_t)b * n_items);
+        offsets.alloc((size_t)n + 1);
+        MI_HIP(hipMemcpyAsync(offsets.ptr, host.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+        MI_HIP(hipStreamSynchronize(s));
+        offsets_n = n; offsets_items = n_items;
+    }
+    hipLaunchKernelGGL(wide_filter_kernel, dim3(std::min(div_up(n_items, 256), 64), n), dim3(256), 0, s, scores, ids_in.ptr, n_items,
+                       users, seen_ptr, seen_idx, allowed, remove_seen);
+    size_t bytes = 0;
+    MI_HIP(rocprim::segmented_radix_sort_pairs_desc(nullptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
+                                                                 n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
+    if (tmp.count < bytes) {
+        MI_HIP(hipStreamSynchronize(s));
+        tmp.alloc(bytes + 256);
+    }
+    bytes = tmp.count;
+    MI_HIP(rocprim::segmented_radix_sort_pairs_desc(tmp.ptr, bytes, scores, keys_out.ptr, ids_in.ptr, ids_out.ptr, (int)total,
+                                                                 n, offsets.ptr, offsets.ptr + 1, 0, 32, s));
+    hipLaunchKernelGGL(wide_emit_kernel, dim3(std::min(div_up(cutoff, 256), 64), n), dim3(256), 0, s, keys_out.ptr, ids_out.ptr, n_items,
+                       cutoff, ranked);
+}
+
+namespace {
 
 bool fits_lds_rank(int n_items, int cutoff) {
     const size_t lds = ((size_t)((n_items + 3) & ~3)) * 4 + (size_t)AUX_WORDS * 4 + 2048;
@@ -314,27 +309,33 @@ bool fits_lds_rank(int n_items, int cutoff) {
 
 using namespace mi355rec;
 
-struct mi355rec_scorer {
-    WideRanker wide;
-    int n_users = 0, n_items = 0, k = 0, use_bias = 0;
-    float mu = 0.f;
-    hipStream_t stream = nullptr;
-    StreamTimer gemm_timer, call_timer;
-    DeviceBuffer<float> U, V, bu, bi, scores;
-    DeviceBuffer<int> seen_ptr, seen_idx, users, ranked;
-    DeviceBuffer<unsigned char> allowed;
-    mi355rec_stats stats{};
-
-    ~mi355rec_scorer() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        gemm_timer.destroy();
-        call_timer.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 namespace {
+// The body of mi355rec_scorer_recommend and mi355rec_spscorer_recommend: user ids and the item mask go up, `enqueue` scores and
+// ranks, the lists (and the score rows, when asked for) come down, `fill_stats` reads the handle's timers.  `bad_user` raises the
+// scorer's own complaint about a user id.
+template <class H, class Enqueue, class BadUser, class FillStats>
+void recommend(H *h, const int32_t *user_ids, int n, int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked,
+               float *scores, Enqueue enqueue, BadUser bad_user, FillStats fill_stats) {
+    MI_REQUIRE(h && user_ids && ranked, "NULL argument");
+    MI_REQUIRE(n > 0, "empty user batch");
+    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
+    for (int i = 0; i < n; ++i)
+        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) bad_user(user_ids[i]);
+    ensure_device();
+    hipStream_t s = h->stream;
+    if (h->users.count < (size_t)n) h->users.alloc(n);
+    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
+    enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
+    h->ranked.download(ranked, (size_t)n * cutoff, s);
+    if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
+    MI_HIP(hipStreamSynchronize(s));
+    h->stats = mi355rec_stats{};
+    fill_stats();
+    h->stats.n_launches = h->stats.n_timed = 1;
+    h->stats.n_units = n;
+}
+
 void upload_model(mi355rec_scorer *h, const float *U, const float *V, const float *bu, const float *bi, float mu) {
     hipStream_t s = h->stream;
     MI_HIP(hipMemcpyAsync(h->U.ptr, U, sizeof(float) * (size_t)h->n_users * h->k, hipMemcpyHostToDevice, s));
@@ -356,12 +357,8 @@ extern "C" int mi355rec_scorer_create(mi355rec_scorer_t *out, int32_t n_users, i
     return guarded([&] {
         MI_REQUIRE(out && U && V && seen_indptr && seen_indices, "NULL argument");
         MI_REQUIRE(n_users > 0 && n_items > 0 && n_factors > 0, "empty model");
-        ensure_device();
-        std::unique_ptr<mi355rec_scorer> h(new mi355rec_scorer());
+        auto h = open_handle<mi355rec_scorer>(2);
         h->n_users = n_users; h->n_items = n_items; h->k = n_factors; h->use_bias = use_bias != 0;
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->gemm_timer.init();
-        h->call_timer.init();
         h->U.alloc((size_t)n_users * n_factors);
         h->V.alloc((size_t)n_items * n_factors);
         if (h->use_bias) { h->bu.alloc(n_users); h->bi.alloc(n_items); }
@@ -411,8 +408,8 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
     sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
     sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
     sp.users = users; sp.n_batch = n; sp.scores = h->scores.ptr;
-    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->gemm_timer.t0,
-                          h->gemm_timer.t1, 0, sp);
+    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->timer.t0,
+                          h->timer.t1, 0, sp);
     if (!wide) {
         RankParams rp{};
         rp.n_items = h->n_items; rp.n_pad = (h->n_items + 3) & ~3; rp.cutoff = cutoff;
@@ -433,52 +430,28 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
     return Ranking{h->ranked.ptr, s};
 }
 
-void scorer_info(mi355rec_scorer_t h, int *n_users, int *n_items, hipStream_t *stream) {
-    *n_users = h->n_users; *n_items = h->n_items; *stream = h->stream;
-}
 }  // namespace mi355rec
 
 extern "C" int mi355rec_scorer_recommend(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                          int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
     return guarded([&] {
-        MI_REQUIRE(h && user_ids && ranked, "NULL argument");
-        MI_REQUIRE(n > 0, "empty user batch");
-        MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-        for (int i = 0; i < n; ++i)
-            MI_REQUIRE(user_ids[i] >= 0 && user_ids[i] < h->n_users, "Cold users not allowed. Users in trained model are %d, "
-                       "requested prediction for user %d", h->n_users, user_ids[i]);
-        ensure_device();
-        hipStream_t s = h->stream;
-        if (h->users.count < (size_t)n) h->users.alloc(n);
-        MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-        scorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
-        h->ranked.download(ranked, (size_t)n * cutoff, s);
-        if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
-        MI_HIP(hipStreamSynchronize(s));
-        h->stats = mi355rec_stats{};
-        h->stats.call_ms = h->call_timer.elapsed_ms();
-        h->stats.kernel_ms = h->gemm_timer.elapsed_ms();
-        h->stats.n_launches = 1;
-        h->stats.n_timed = 1;
-        h->stats.n_units = n;
-        h->stats.algorithmic_flops = 2.0 * (double)n * h->n_items * h->k;
-        h->stats.algorithmic_bytes = 4.0 * ((double)n * h->k + (double)h->n_items * h->k + (double)n * h->n_items);
+        recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores, scorer_enqueue,
+                  [&](int u) {
+                      fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d",
+                           h->n_users, u);
+                  },
+                  [&] {
+                      h->stats.call_ms = h->call_timer.elapsed_ms();
+                      h->stats.kernel_ms = h->timer.elapsed_ms();
+                      h->stats.algorithmic_flops = 2.0 * (double)n * h->n_items * h->k;
+                      h->stats.algorithmic_bytes = 4.0 * ((double)n * h->k + (double)h->n_items * h->k + (double)n * h->n_items);
+                  });
     });
 }
 
-extern "C" int mi355rec_scorer_get_stats(mi355rec_scorer_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_scorer_get_stats(mi355rec_scorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
-extern "C" void mi355rec_scorer_destroy(mi355rec_scorer_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_scorer_destroy(mi355rec_scorer_t h) { handle_destroy(h); }
 
 // ------------------------------------------------------------------------------------------------------
 // Similarity-model scoring: scores[u] = A[u, :] . B with A and B sparse (CSR).
@@ -563,25 +536,6 @@ __global__ __launch_bounds__(1024) void spscore_wide_kernel(const SpScoreParams 
 }  // namespace
 }  // namespace mi355rec
 
-struct mi355rec_spscorer {
-    WideRanker wide;
-    int n_users = 0, n_mid = 0, n_out = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer timer;
-    DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx, seen_ptr, seen_idx, users, ranked;
-    DeviceBuffer<float> a_val, b_val, scores;
-    DeviceBuffer<unsigned char> allowed;
-    mi355rec_stats stats{};
-    double nnz_a = 0, nnz_b = 0;
-
-    ~mi355rec_spscorer() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        timer.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 extern "C" int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_users, int32_t n_mid, int32_t n_out,
                                         const int32_t *a_indptr, const int32_t *a_indices, const float *a_data,
                                         const int32_t *b_indptr, const int32_t *b_indices, const float *b_data,
@@ -589,11 +543,8 @@ extern "C" int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_user
     return guarded([&] {
         MI_REQUIRE(out && a_indptr && a_indices && a_data && b_indptr && b_indices && b_data && seen_indptr && seen_indices, "NULL argument");
         MI_REQUIRE(n_users > 0 && n_mid > 0 && n_out > 0, "empty model");
-        ensure_device();
-        std::unique_ptr<mi355rec_spscorer> h(new mi355rec_spscorer());
-        h->n_users = n_users; h->n_mid = n_mid; h->n_out = n_out;
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->timer.init();
+        auto h = open_handle<mi355rec_spscorer>(1);
+        h->n_users = n_users; h->n_mid = n_mid; h->n_items = n_out;
         hipStream_t s = h->stream;
         const size_t na = (size_t)a_indptr[n_users], nb = (size_t)b_indptr[n_mid], ns = (size_t)seen_indptr[n_users];
         h->a_ptr.upload(a_indptr, (size_t)n_users + 1, s);
@@ -616,16 +567,16 @@ namespace mi355rec {
 Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                          bool keep_scores) {
     hipStream_t s = h->stream;
-    const bool in_lds = fits_lds_rank(h->n_out, cutoff);
+    const bool in_lds = fits_lds_rank(h->n_items, cutoff);
     const bool need_scores = keep_scores || !in_lds;
-    if (h->ranked.count < (size_t)n * cutoff || (need_scores && h->scores.count < (size_t)n * h->n_out) ||
-        (!in_lds && h->wide.capacity < (size_t)n * h->n_out)) {
+    if (h->ranked.count < (size_t)n * cutoff || (need_scores && h->scores.count < (size_t)n * h->n_items) ||
+        (!in_lds && h->wide.capacity < (size_t)n * h->n_items)) {
         MI_HIP(hipStreamSynchronize(s));
         if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
-        if (need_scores && h->scores.count < (size_t)n * h->n_out) h->scores.alloc((size_t)n * h->n_out);
+        if (need_scores && h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
     }
     SpScoreParams p{};
-    p.n_out = h->n_out; p.n_pad = (h->n_out + 3) & ~3; p.cutoff = cutoff;
+    p.n_out = h->n_items; p.n_pad = (h->n_items + 3) & ~3; p.cutoff = cutoff;
     p.remove_seen = remove_seen; p.write_back = keep_scores;
     p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
     p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
@@ -638,52 +589,26 @@ Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cut
         MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipExtLaunchKernelGGL(k, dim3(n), dim3(1024), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
     } else {
-        MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_out, s));
+        MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_items, s));
         hipExtLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, h->timer.t0, h->timer.t1, 0, p);
-        h->wide.rank(s, h->scores.ptr, n, h->n_out, cutoff, users, h->seen_ptr.ptr, h->seen_idx.ptr, p.allowed, remove_seen,
+        h->wide.rank(s, h->scores.ptr, n, h->n_items, cutoff, users, h->seen_ptr.ptr, h->seen_idx.ptr, p.allowed, remove_seen,
                      h->ranked.ptr);
     }
     MI_HIP(hipGetLastError());
     return Ranking{h->ranked.ptr, s};
 }
 
-void spscorer_info(mi355rec_spscorer_t h, int *n_users, int *n_items, hipStream_t *stream) {
-    *n_users = h->n_users; *n_items = h->n_out; *stream = h->stream;
-}
 }  // namespace mi355rec
 
 extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                            int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
     return guarded([&] {
-        MI_REQUIRE(h && user_ids && ranked, "NULL argument");
-        MI_REQUIRE(n > 0, "empty user batch");
-        MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_out, "cutoff must be in [1, n_items]");
-        for (int i = 0; i < n; ++i) MI_REQUIRE(user_ids[i] >= 0 && user_ids[i] < h->n_users, "user id %d out of range", user_ids[i]);
-        ensure_device();
-        hipStream_t s = h->stream;
-        if (h->users.count < (size_t)n) h->users.alloc(n);
-        MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_out, hipMemcpyHostToDevice, s));
-        spscorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
-        h->ranked.download(ranked, (size_t)n * cutoff, s);
-        if (scores) h->scores.download(scores, (size_t)n * h->n_out, s);
-        MI_HIP(hipStreamSynchronize(s));
-        h->stats = mi355rec_stats{};
-        h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms();
-        h->stats.n_launches = h->stats.n_timed = 1;
-        h->stats.n_units = n;
+        recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores, spscorer_enqueue,
+                  [](int u) { fail(MI355REC_E_INVALID, "user id %d out of range", u); },
+                  [&] { h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms(); });
     });
 }
 
-extern "C" int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
-extern "C" void mi355rec_spscorer_destroy(mi355rec_spscorer_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_spscorer_destroy(mi355rec_spscorer_t h) { handle_destroy(h); }

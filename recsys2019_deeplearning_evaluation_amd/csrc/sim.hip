@@ -1877,14 +1877,12 @@ __global__ void transpose_kernel(const float *in, float *out, int rows, int cols
 
 using namespace mi355rec;
 
-struct mi355rec_sim {
+struct mi355rec_sim : Handle {     // `timer`: start/stop events carried by the column-kernel dispatch itself; `call_timer`: events
+                                   // around the whole call (H2D of the schedule, kernel, D2H of the result)
     mi355rec_sim_config cfg{};
     int n_rows = 0, n_cols = 0;
     size_t nnz = 0;
     bool unit_values = false;
-    hipStream_t stream = nullptr;
-    StreamTimer timer;       // start/stop events carried by the column-kernel dispatch itself
-    StreamTimer call_timer;  // events around the whole call (H2D of the schedule, kernel, D2H of the result)
     DeviceBuffer<int> csr_ptr, csr_idx, csc_ptr, csc_idx;
     DeviceBuffer<int4> items;
     DeviceBuffer<uint32_t> part_buf;
@@ -1924,17 +1922,10 @@ struct mi355rec_sim {
     double wide_kernel_ms = -1.0, wide_call_ms = 0.0;   // >= 0 after a build with topK > MAX_TOPK (several launches: the event pair of the last one is not the build)
     int int_shift = -1;            // >= 0: every stored value times 2^int_shift is a small integer -> exact int32 sums (ACC_INT32)
     int acc_mode() const { return unit_values && !row_w.ptr ? ACC_COUNTS : (int_shift >= 0 ? ACC_INT32 : ACC_WIDE); }
-    mi355rec_stats stats{};
     // last call
     int last_start = -1, last_end = -1;
 
-    ~mi355rec_sim() {   // also runs when mi355rec_sim_create fails half-way: nothing leaks
-        if (stream) (void)hipStreamSynchronize(stream);
-        timer.destroy();
-        call_timer.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) pooled_stream_return(stream);
-    }
+    ~mi355rec_sim() { shutdown(); }
 };
 
 namespace {
@@ -2485,10 +2476,8 @@ static int sim_create_from(mi355rec_sim_t *out, const mi355rec_sim_config *cfg, 
         else nnz_in = csr_indptr[n_rows];
         h->nnz = (size_t)nnz_in;
         MI_REQUIRE(nnz_in > 0, "matrix has no stored values");
-        h->stream = pooled_stream();
+        h->open(2, StreamFrom::Pool);
         ReleaseScope scope(h->stream);          // the constructor's temporaries wait for this stream, not for the device
-        h->timer.init_pooled();
-        h->call_timer.init_pooled();
         hipStream_t s = h->stream;
         const size_t nnz = h->nnz;
         // MI355REC_SIM_CREATE_PHASES=1: wall clock of the constructor's phases on stderr (each one drained before the next starts)
@@ -3270,15 +3259,6 @@ extern "C" int mi355rec_sim_sync(mi355rec_sim_t h) {
     });
 }
 
-extern "C" int mi355rec_sim_get_stats(mi355rec_sim_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_sim_get_stats(mi355rec_sim_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
-extern "C" void mi355rec_sim_destroy(mi355rec_sim_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_sim_destroy(mi355rec_sim_t h) { handle_destroy(h); }

@@ -1479,14 +1479,11 @@ struct StreamSet {
     long long n_cells = 0;
 };
 
-struct mi355rec_slim {
+struct mi355rec_slim : Handle {                        // `side`: schedules of the next epoch
     mi355rec_slim_config cfg{};
     int n_users = 0, n_items = 0;
     bool f64 = false;           // arithmetic type; storage type of the dense store and its optimiser cells
     size_t nnz = 0;
-    hipStream_t stream = nullptr, side = nullptr;       // `side`: schedules of the next epoch
-    StreamTimer call_timer;
-    DispatchTimers dispatch_timers;
     StreamSet set[2];
     int cur = 0;                                        // the set whose stream ran last
     bool last_native = false;                           // ... and whether that was an epoch of the on-device sampler
@@ -1512,18 +1509,8 @@ struct mi355rec_slim {
     unsigned tag_base = 0;                              // symmetric store: tags handed out so far
     int last_owners = 0, last_cold = 0;                 // owned rows / steps on rows in HBM of the last dense launch (diagnostics)
     std::vector<double> h_loss;
-    mi355rec_stats stats{};
 
-    ~mi355rec_slim() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (side) (void)hipStreamSynchronize(side);
-        call_timer.destroy();
-        dispatch_timers.destroy();
-        ReleaseScope::forget(side);
-        ReleaseScope::forget(stream);
-        if (side) (void)hipStreamDestroy(side);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~mi355rec_slim() { shutdown(); }
 };
 
 namespace {
@@ -2076,17 +2063,17 @@ void begin_call(mi355rec_slim *h) {
     MI_HIP(hipMemsetAsync(h->loss_slots.ptr, 0, sizeof(double) * LOSS_SLOTS, h->stream));
     h->dispatch_timers.reset();
     h->stats = mi355rec_stats{};
-    h->call_timer.start(h->stream);
+    h->timer.start(h->stream);
 }
 
 void end_call(mi355rec_slim *h, long long n_steps, double sum_profile) {
-    h->call_timer.stop(h->stream);
+    h->timer.stop(h->stream);
     h->h_loss.resize(LOSS_SLOTS);
     h->loss_slots.download(h->h_loss.data(), LOSS_SLOTS, h->stream);
     MI_HIP(hipStreamSynchronize(h->stream));
     double loss = 0;
     for (double v : h->h_loss) loss += v;
-    h->stats.call_ms = h->call_timer.elapsed_ms();
+    h->stats.call_ms = h->timer.elapsed_ms();
     h->stats.kernel_ms = h->dispatch_timers.total_ms();
     h->stats.n_timed = h->dispatch_timers.used;
     h->stats.n_units = n_steps;
@@ -2322,9 +2309,8 @@ extern "C" int mi355rec_slim_create(mi355rec_slim_t *out, const mi355rec_slim_co
         h->f64 = cfg->precision == MI355REC_F64 || h->cfg.symmetric;
         h->nnz = (size_t)indptr[n_users];
         MI_REQUIRE(h->nnz > 0, "URM has no interactions");
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        MI_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-        h->call_timer.init();
+        h->open(1);
+        h->open_side();
         h->dispatch_timers.reserve(64);
         hipStream_t s = h->stream;
         const size_t ts = h->f64 ? sizeof(double) : sizeof(float);
@@ -2472,12 +2458,7 @@ extern "C" int mi355rec_slim_get_S_dense(mi355rec_slim_t h, float *S) {
     });
 }
 
-extern "C" int mi355rec_slim_get_stats(mi355rec_slim_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_slim_get_stats(mi355rec_slim_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
 extern "C" int mi355rec_slim_schedule_info(mi355rec_slim_t h, int32_t *n_owned_rows, int32_t *n_cold_steps) {
     return guarded([&] {
@@ -2487,8 +2468,4 @@ extern "C" int mi355rec_slim_schedule_info(mi355rec_slim_t h, int32_t *n_owned_r
     });
 }
 
-extern "C" void mi355rec_slim_destroy(mi355rec_slim_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream, h->side);
-    delete h;
-}
+extern "C" void mi355rec_slim_destroy(mi355rec_slim_t h) { handle_destroy(h); }

@@ -426,10 +426,8 @@ std::vector<uint32_t> jump_tables() {
 
 }  // namespace
 
-struct mi355rec_slimen {
+struct mi355rec_slimen : Handle {                     // `timer`: the fit kernel; `call_timer`: the Gram build of create
     int n_users = 0, n_items = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer call_timer, kernel_timer;
     DeviceBuffer<float> G, diag, w_slots, h_slots, out_val;
     DeviceBuffer<int> out_idx, out_n, out_iter, out_conv;
     DeviceBuffer<uint32_t> seeds, jump;
@@ -438,15 +436,8 @@ struct mi355rec_slimen {
     int n_targets = 0, slots_per_target = 0, h_in_lds = 0;
     double gram_ms = 0.0;
     unsigned long long counts[4] = {0, 0, 0, 0};
-    mi355rec_stats stats{};
 
-    ~mi355rec_slimen() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        call_timer.destroy();
-        kernel_timer.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~mi355rec_slimen() { shutdown(); }
 };
 
 extern "C" int mi355rec_slimen_create(mi355rec_slimen_t *out, int32_t n_users, int32_t n_items, const int32_t *row_ptr,
@@ -456,13 +447,9 @@ extern "C" int mi355rec_slimen_create(mi355rec_slimen_t *out, int32_t n_users, i
         MI_REQUIRE(out && row_ptr && col_ptr, "NULL argument");
         MI_REQUIRE(n_users > 0 && n_items > 0, "empty URM (%d x %d)", n_users, n_items);
         *out = nullptr;
-        ensure_device();
-        std::unique_ptr<mi355rec_slimen> h(new mi355rec_slimen());
+        auto h = open_handle<mi355rec_slimen>(2);
         h->n_users = n_users;
         h->n_items = n_items;
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->call_timer.init();
-        h->kernel_timer.init();
         ReleaseScope scope(h->stream);
         hipStream_t s = h->stream;
         const size_t g_bytes = (size_t)n_items * n_items * sizeof(float);
@@ -567,7 +554,7 @@ extern "C" int mi355rec_slimen_fit(mi355rec_slimen_t h, int32_t start_item, int3
         a.out_iter = h->out_iter.ptr;
         a.out_conv = h->out_conv.ptr;
         a.counters = h->counters.ptr;
-        h->kernel_timer.start(s);
+        h->timer.start(s);
         if (n_t > 0) {
             if (h->h_in_lds) {
                 auto k = slimen_fit_kernel<true>;
@@ -578,10 +565,10 @@ extern "C" int mi355rec_slimen_fit(mi355rec_slimen_t h, int32_t start_item, int3
             }
             MI_HIP(hipGetLastError());
         }
-        h->kernel_timer.stop(s);
+        h->timer.stop(s);
         MI_HIP(hipMemcpyAsync(h->counts, h->counters.ptr, sizeof(h->counts), hipMemcpyDeviceToHost, s));
         MI_HIP(hipStreamSynchronize(s));
-        const double ms = h->kernel_timer.elapsed_ms();
+        const double ms = h->timer.elapsed_ms();
         h->stats = mi355rec_stats{};
         h->stats.call_ms = ms;
         h->stats.kernel_ms = ms;
@@ -610,12 +597,7 @@ extern "C" int mi355rec_slimen_get(mi355rec_slimen_t h, int32_t *counts, int32_t
     });
 }
 
-extern "C" int mi355rec_slimen_get_stats(mi355rec_slimen_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_slimen_get_stats(mi355rec_slimen_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
 extern "C" int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, int64_t *sweeps, int64_t *steps, int64_t *gap_tests,
                                         int32_t *h_in_lds, double *gram_ms) {
@@ -630,8 +612,4 @@ extern "C" int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, i
     });
 }
 
-extern "C" void mi355rec_slimen_destroy(mi355rec_slimen_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_slimen_destroy(mi355rec_slimen_t h) { handle_destroy(h); }

@@ -221,28 +221,20 @@ struct Side {
 
 }  // namespace
 
-struct mi355rec_svd {
+struct mi355rec_svd : Handle {
     int n_users = 0, n_items = 0, r = 0, ones = 0;
     size_t nnz = 0;
-    hipStream_t stream = nullptr;
-    StreamTimer timer;
-    Side side[2];                                     // [0]: rows = users (the CSR layout), [1]: rows = items (the CSC layout)
+    Side sides[2];                                     // [0]: rows = users (the CSR layout), [1]: rows = items (the CSC layout)
     DeviceBuffer<float> block[2], tmp, partial, T;
     DeviceBuffer<double> gram_part, G;
     DeviceBuffer<int> iota;
     int gram_slabs[2] = {0, 0}, gram_rows[2] = {0, 0};
     double phase_ms[3] = {0, 0, 0};                   // products, Gram, apply
     int64_t launches = 0, calls = 0, create_bytes = 0, h2d_bytes = 0, d2h_bytes = 0;
-    mi355rec_stats stats{};
 
     int rows_of(int s) const { return s == 0 ? n_users : n_items; }
 
-    ~mi355rec_svd() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        timer.destroy();
-        ReleaseScope::forget(stream);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
+    ~mi355rec_svd() { shutdown(); }
 };
 
 extern "C" int mi355rec_svd_create(mi355rec_svd_t *out, int32_t n_users, int32_t n_items, int32_t r, const int32_t *row_ptr,
@@ -259,8 +251,7 @@ extern "C" int mi355rec_svd_create(mi355rec_svd_t *out, int32_t n_users, int32_t
         validate_layout(n_users, n_items, row_ptr, row_idx);
         validate_layout(n_items, n_users, col_ptr, col_idx);
         *out = nullptr;
-        ensure_device();
-        std::unique_ptr<mi355rec_svd> h(new mi355rec_svd());
+        auto h = open_handle<mi355rec_svd>(1);
         h->n_users = n_users;
         h->n_items = n_items;
         h->r = r;
@@ -268,17 +259,15 @@ extern "C" int mi355rec_svd_create(mi355rec_svd_t *out, int32_t n_users, int32_t
         bool ones = true;
         for (size_t i = 0; i < nnz && ones; ++i) ones = row_val[i] == 1.0f;
         h->ones = ones ? 1 : 0;
-        MI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->timer.init();
         ReleaseScope scope(h->stream);
         hipStream_t s = h->stream;
-        h->create_bytes += (int64_t)h->side[0].build(n_users, row_ptr, row_idx, row_val, ones, s);
-        h->create_bytes += (int64_t)h->side[1].build(n_items, col_ptr, col_idx, col_val, ones, s);
+        h->create_bytes += (int64_t)h->sides[0].build(n_users, row_ptr, row_idx, row_val, ones, s);
+        h->create_bytes += (int64_t)h->sides[1].build(n_items, col_ptr, col_idx, col_val, ones, s);
         const size_t cap = (size_t)std::max(n_users, n_items) * r;
         h->block[0].alloc_zero(cap, s);
         h->block[1].alloc_zero(cap, s);
         h->tmp.alloc(cap);
-        h->partial.alloc((size_t)std::max(1, std::max(h->side[0].n_slots, h->side[1].n_slots)) * r);
+        h->partial.alloc((size_t)std::max(1, std::max(h->sides[0].n_slots, h->sides[1].n_slots)) * r);
         const int nt = div_up(r, GT), pairs = nt * (nt + 1) / 2;
         size_t part_cells = 1;
         for (int sd = 0; sd < 2; ++sd) {
@@ -332,7 +321,7 @@ extern "C" int mi355rec_svd_product(mi355rec_svd_t h, int32_t dst_side) {
         MI_REQUIRE(dst_side == 0 || dst_side == 1, "side %d: 0 (users = URM . items) or 1 (items = URM^T . users)", dst_side);
         ensure_device();
         hipStream_t s = h->stream;
-        const Side &sd = h->side[dst_side];
+        const Side &sd = h->sides[dst_side];
         const int r = h->r;
         const int lp_shift = r <= 16 ? 4 : (r <= 32 ? 5 : 6);
         const float *X = h->block[1 - dst_side].ptr;
@@ -413,12 +402,7 @@ extern "C" int mi355rec_svd_apply(mi355rec_svd_t h, int32_t side, const float *T
     });
 }
 
-extern "C" int mi355rec_svd_get_stats(mi355rec_svd_t h, mi355rec_stats *stats) {
-    return guarded([&] {
-        MI_REQUIRE(h && stats, "NULL argument");
-        *stats = h->stats;
-    });
-}
+extern "C" int mi355rec_svd_get_stats(mi355rec_svd_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
 extern "C" int mi355rec_svd_fit_info(mi355rec_svd_t h, double *product_ms, double *gram_ms, double *apply_ms, int64_t *launches,
                                      int64_t *calls, int64_t *create_bytes, int64_t *h2d_bytes, int64_t *d2h_bytes, int32_t *all_ones) {
@@ -437,8 +421,4 @@ extern "C" int mi355rec_svd_fit_info(mi355rec_svd_t h, double *product_ms, doubl
     });
 }
 
-extern "C" void mi355rec_svd_destroy(mi355rec_svd_t h) {
-    if (!h) return;
-    ReleaseScope scope(h->stream);
-    delete h;
-}
+extern "C" void mi355rec_svd_destroy(mi355rec_svd_t h) { handle_destroy(h); }

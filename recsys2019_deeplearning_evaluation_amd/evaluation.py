@@ -98,8 +98,9 @@ def item_terms(URM_train):
     return novelty, popularity_norm
 
 
-class EvaluatorHoldout_MI355X:
+class EvaluatorHoldout_MI355X(N.Handle):
     """EvaluatorHoldout (Evaluator.py:382) on the device.  See the module docstring."""
+    _PREFIX = "mi355rec_eval"
 
     EVALUATOR_NAME = "EvaluatorHoldout_MI355X"
 
@@ -149,10 +150,8 @@ class EvaluatorHoldout_MI355X:
         log_len = max(self.width, longest, 1)
         log_table = np.log(np.arange(log_len, dtype=np.float32) + 2)                  # dcg (metrics.py:207-209)
         cutoffs = np.asarray(self.cutoff_list, dtype=np.int32)
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_eval_create(C.byref(self._h), self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices),
-                                               N.ptr(relevance), N.ptr(cutoffs), len(cutoffs), N.ptr(log_table), log_len))
+        self._create(self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices), N.ptr(relevance), N.ptr(cutoffs), len(cutoffs),
+                     N.ptr(log_table), log_len)
         self._per_user = None
         self.item_counts = None             # {cutoff: times each item was recommended within the cutoff}, last evaluation
 
@@ -182,17 +181,17 @@ class EvaluatorHoldout_MI355X:
                 self._per_user = np.zeros((0, len(self.cutoff_list), N_VALUES))
                 results = {c: {m: 0.0 for m in METRICS} for c in self.cutoff_list}
                 return results, get_result_string(results)
-            N.check(self._lib.mi355rec_eval_begin(self._h, N.ptr(novelty), N.ptr(popularity_norm), N.ptr(users), n_eval))
+            self._call("begin", N.ptr(novelty), N.ptr(popularity_norm), N.ptr(users), n_eval)
             block = int(block_size) if block_size else self._block_size()
             if isinstance(rec, GpuScoringMixin):
-                self._run_fused(rec._get_scorer(), self._lib.mi355rec_eval_add_scorer, rec, block)
+                self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
             elif isinstance(rec, GpuSimilarityScoringMixin):
-                self._run_fused(rec._get_sparse_scorer(), self._lib.mi355rec_eval_add_spscorer, rec, block)
+                self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
             else:
                 self._run_lists(rec, block)
             sums = np.zeros((len(self.cutoff_list), N_VALUES), np.float64)
             counts = np.zeros((len(self.cutoff_list), self.n_items), np.int32)
-            N.check(self._lib.mi355rec_eval_finish(self._h, N.ptr(sums), N.ptr(counts)))
+            self._call("finish", N.ptr(sums), N.ptr(counts))
         finally:
             if self.ignore_items_flag:
                 rec.reset_items_to_ignore()
@@ -216,7 +215,7 @@ class EvaluatorHoldout_MI355X:
         allowed = allowed_items(rec, remove_custom_items_flag=self.ignore_items_flag)
         for start in range(0, len(self.users_to_evaluate), block):
             n = min(block, len(self.users_to_evaluate) - start)
-            N.check(add(self._h, scorer._h, start, n, int(bool(self.exclude_seen)), N.ptr(allowed)))
+            self._call(add, scorer._h, start, n, int(bool(self.exclude_seen)), N.ptr(allowed))
 
     def _run_lists(self, rec, block):
         users = self.users_to_evaluate
@@ -234,7 +233,7 @@ class EvaluatorHoldout_MI355X:
                 if len(items) and (items.min() < 0 or items.max() >= self.n_items):
                     raise ValueError("{}: recommended item id outside [0, {})".format(self.EVALUATOR_NAME, self.n_items))
                 table[r, :len(items)] = items
-            N.check(self._lib.mi355rec_eval_add_lists(self._h, start, len(batch), N.ptr(table)))
+            self._call("add_lists", start, len(batch), N.ptr(table))
 
     def per_user_values(self):
         """{cutoff: {metric: float64 array}} of the last evaluation, one entry per evaluated user in `users_to_evaluate` order:
@@ -245,18 +244,7 @@ class EvaluatorHoldout_MI355X:
                 self._per_user = np.zeros((0, len(self.cutoff_list), N_VALUES))
             else:
                 out = np.zeros((n_eval, len(self.cutoff_list), N_VALUES), np.float64)
-                N.check(self._lib.mi355rec_eval_get_per_user(self._h, N.ptr(out)))
+                self._call("get_per_user", N.ptr(out))
                 self._per_user = out
         return {cutoff: {m: self._per_user[:, c, v].copy() for v, m in enumerate(PER_USER)}
                 for c, cutoff in enumerate(self.cutoff_list)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_eval_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -15,8 +15,9 @@ from .recommender_base import (BaseMatrixFactorizationRecommender, Incremental_T
 from .scoring import GpuScoringMixin
 
 
-class IALS_MI355X_Epoch:
+class IALS_MI355X_Epoch(N.Handle):
     """Device-resident IALS state: one object per fit(), like the Cython epoch objects of the SGD recommenders."""
+    _PREFIX = "mi355rec_ials"
 
     def __init__(self, C_csr, num_factors, reg, ITEM_factors, USER_factors=None):
         C_csr = check_matrix(C_csr, "csr", dtype=np.float32)
@@ -28,55 +29,37 @@ class IALS_MI355X_Epoch:
         V0 = np.ascontiguousarray(ITEM_factors, dtype=np.float64)
         U0 = None if USER_factors is None else np.ascontiguousarray(USER_factors, dtype=np.float64)
         assert V0.shape == (self.n_items, self.num_factors)
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_ials_create(C.byref(self._h), self.n_users, self.n_items, self.num_factors, float(reg),
-                                               N.ptr(indptr), N.ptr(indices), N.ptr(conf), N.ptr(U0), N.ptr(V0)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_ials_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(self.n_users, self.n_items, self.num_factors, float(reg), N.ptr(indptr), N.ptr(indices), N.ptr(conf), N.ptr(U0),
+                     N.ptr(V0))
 
     def run_epochs(self, n_epochs=1):
-        N.check(self._lib.mi355rec_ials_run_epochs(self._h, int(n_epochs)))
+        self._call("run_epochs", int(n_epochs))
 
     def user_half(self, u0, u1):
-        N.check(self._lib.mi355rec_ials_user_half(self._h, int(u0), int(u1)))
+        self._call("user_half", int(u0), int(u1))
 
     def item_half(self, i0, i1):
-        N.check(self._lib.mi355rec_ials_item_half(self._h, int(i0), int(i1)))
+        self._call("item_half", int(i0), int(i1))
 
     def synchronize(self):
-        N.check(self._lib.mi355rec_ials_sync(self._h))
+        self._call("sync")
 
     def device_factor_pointers(self):
         dU, dV = C.c_void_p(), C.c_void_p()
-        N.check(self._lib.mi355rec_ials_device_factors(self._h, C.byref(dU), C.byref(dV)))
+        self._call("device_factors", C.byref(dU), C.byref(dV))
         return dU.value, dV.value
 
     def get_factors(self):
         U = np.empty((self.n_users, self.num_factors), np.float64)
         V = np.empty((self.n_items, self.num_factors), np.float64)
-        N.check(self._lib.mi355rec_ials_get_factors(self._h, N.ptr(U), N.ptr(V)))
+        self._call("get_factors", N.ptr(U), N.ptr(V))
         return U, V
 
     def schedule_info(self):
         """(rows split over several workgroups, parts) of the last half-step."""
         a, b = C.c_int32(), C.c_int32()
-        N.check(self._lib.mi355rec_ials_schedule_info(self._h, C.byref(a), C.byref(b)))
+        self._call("schedule_info", C.byref(a), C.byref(b))
         return a.value, b.value
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_ials_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
 
 
 class _IALSLogic:

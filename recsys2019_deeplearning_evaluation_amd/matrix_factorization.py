@@ -24,7 +24,8 @@ from .recommender_base import (BaseMatrixFactorizationRecommender, Incremental_T
 from .scoring import GpuScoringMixin
 
 
-class MatrixFactorization_MI355X_Epoch:
+class MatrixFactorization_MI355X_Epoch(N.Handle):
+    _PREFIX = "mi355rec_mf"
     SGD_MODE_VALUES = ["sgd", "adam", "adagrad", "rmsprop"]
     ALGORITHM_NAME_VALUES = ["FUNK_SVD", "ASY_SVD", "MF_BPR"]
 
@@ -78,26 +79,12 @@ class MatrixFactorization_MI355X_Epoch:
                          N.PRECISION_CODES[precision], 0)
         indptr, indices, data = N.as_i32(URM_train.indptr), N.as_i32(URM_train.indices), N.as_f32(URM_train.data)
         U0, V0 = (N.as_f64(U0), N.as_f64(V0)) if precision == "fp64" else (N.as_f32(U0), N.as_f32(V0))
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_mf_create(C.byref(self._h), C.byref(cfg), self.n_users, self.n_items,
-                                             N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(U0), N.ptr(V0)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_mf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(C.byref(cfg), self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(U0), N.ptr(V0))
 
     # ---- training ----
     def epochIteration_Cython(self, n_epochs=1):
         """One reference epoch (n_users/B+1 or nnz/B+1 mini-batches); n_epochs>1 fuses several into one call."""
-        N.check(self._lib.mi355rec_mf_run_epochs(self._h, int(n_epochs)))
+        self._call("run_epochs", int(n_epochs))
         if self.verbose:
             st = self.stats()
             print("{}: Processed {} samples in {:.3f} seconds. loss {:.2E}. Sample per second: {:.0f}".format(
@@ -109,41 +96,36 @@ class MatrixFactorization_MI355X_Epoch:
         user, item = N.as_i32(user), N.as_i32(item)
         neg_item = None if neg_item is None else N.as_i32(neg_item)
         rating = None if rating is None else N.as_f32(rating)
-        N.check(self._lib.mi355rec_mf_run_samples(self._h, N.ptr(user), N.ptr(item), N.ptr(neg_item), N.ptr(rating), len(user)))
+        self._call("run_samples", N.ptr(user), N.ptr(item), N.ptr(neg_item), N.ptr(rating), len(user))
 
     def last_epoch_samples(self):
         """(user, item, neg_item | rating) drawn on the device during the last epoch of the last native call."""
         n = C.c_int64(0)
-        N.check(self._lib.mi355rec_mf_get_last_samples(self._h, None, None, None, None, 0, C.byref(n)))
+        self._call("get_last_samples", None, None, None, None, 0, C.byref(n))
         u = np.empty(n.value, np.int32); i = np.empty(n.value, np.int32)
         j = np.empty(n.value, np.int32); r = np.empty(n.value, np.float32)
-        N.check(self._lib.mi355rec_mf_get_last_samples(self._h, N.ptr(u), N.ptr(i), N.ptr(j), N.ptr(r), n.value, C.byref(n)))
+        self._call("get_last_samples", N.ptr(u), N.ptr(i), N.ptr(j), N.ptr(r), n.value, C.byref(n))
         return (u, i, j) if self.algorithm_name == "MF_BPR" else (u, i, r)
 
     # ---- exact multi-GPU mini-batches (sharding.sharded_bpr_epoch drives these) ----
     def shard_begin_epoch(self, rank, world):
         """Draws and schedules one epoch; returns (send address, receive address, bytes per rank, mini-batches)."""
         send, recv, nbytes, nb = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_int32()
-        N.check(self._lib.mi355rec_mf_shard_begin_epoch(self._h, int(rank), int(world), C.byref(send), C.byref(recv), C.byref(nbytes), C.byref(nb)))
+        self._call("shard_begin_epoch", int(rank), int(world), C.byref(send), C.byref(recv), C.byref(nbytes), C.byref(nb))
         return send.value, recv.value, nbytes.value, nb.value
 
     def shard_batch(self, batch):
-        N.check(self._lib.mi355rec_mf_shard_batch(self._h, int(batch)))
+        self._call("shard_batch", int(batch))
 
     def shard_merge(self, batch):
-        N.check(self._lib.mi355rec_mf_shard_merge(self._h, int(batch)))
+        self._call("shard_merge", int(batch))
 
     def shard_end_epoch(self):
-        N.check(self._lib.mi355rec_mf_shard_end_epoch(self._h))
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_mf_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
+        self._call("shard_end_epoch")
 
     def set_profiling(self, max_timed_launches):
         """Attach start/stop events to (at most) that many gradient-kernel dispatches of every following call."""
-        N.check(self._lib.mi355rec_mf_set_profiling(self._h, int(max_timed_launches)))
+        self._call("set_profiling", int(max_timed_launches))
 
     # ---- model read-back (fresh host copies; float64 like the reference's getters, .pyx:685-702, when the device state is
     # float64 -- adagrad / rmsprop / adam, AsySVD -- and the float32 state as it is otherwise) ----
@@ -155,8 +137,7 @@ class MatrixFactorization_MI355X_Epoch:
         bu = bi = mu = None
         if want_bias:
             bu = np.empty(self.n_users, dt); bi = np.empty(self.n_items, dt); mu = np.empty(1, dt)
-        get = self._lib.mi355rec_mf_get_factors_f64 if f64 else self._lib.mi355rec_mf_get_factors
-        N.check(get(self._h, N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), N.ptr(mu)))
+        self._call("get_factors_f64" if f64 else "get_factors", N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), N.ptr(mu))
         return U, V, bu, bi, mu
 
     def get_factors(self):
@@ -179,7 +160,7 @@ class MatrixFactorization_MI355X_Epoch:
         return np.array(self._download(True)[4][0])
 
 
-class MatrixFactorization_MI355X_Group:
+class MatrixFactorization_MI355X_Group(N.Handle):
     """R independent epoch objects trained side by side: mini-batch b of ALL members is ONE launch (mi355rec_mf_group_*).
 
     The reference's hyper-parameter search runs this path as a pool of workers with one model each
@@ -188,15 +169,14 @@ class MatrixFactorization_MI355X_Group:
     hyper-parameters, optimiser, seed and sample stream and end bit-identical to training alone; they must share
     algorithm_name (MF_BPR / FUNK_SVD), precision, batch_size, the URM's number of mini-batches per epoch and the kernel
     instance n_factors selects (see include/mi355rec.h).  The group does not own its members."""
+    _PREFIX = "mi355rec_mf_group"
 
     def __init__(self, members):
         self.members = list(members)
         assert len(self.members) >= 1
-        self._lib = N.load()
         handles = (C.c_void_p * len(self.members))(*[m._h for m in self.members])
         self._member_handles = [m._h.value for m in self.members]      # the native group keeps these raw handles
-        self._g = C.c_void_p()
-        N.check(self._lib.mi355rec_mf_group_create(C.byref(self._g), handles, len(self.members)))
+        self._create(handles, len(self.members))
 
     def epochIteration_Cython(self, n_epochs=1):
         # a member that was closed (or closed and re-created) since the group was built would be a dangling handle on the device side
@@ -204,26 +184,10 @@ class MatrixFactorization_MI355X_Group:
             if getattr(m, "_h", None) is None or m._h.value != h:
                 raise RuntimeError("MatrixFactorization_MI355X_Group: member %d was closed after the group was created; "
                                    "build a new group from live epoch objects" % n)
-        N.check(self._lib.mi355rec_mf_group_run_epochs(self._g, int(n_epochs)))
+        self._call("run_epochs", int(n_epochs))
 
     def set_profiling(self, max_timed_launches):
-        N.check(self._lib.mi355rec_mf_group_set_profiling(self._g, int(max_timed_launches)))
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_mf_group_get_stats(self._g, C.byref(st)))
-        return st.as_dict()
-
-    def close(self):
-        if getattr(self, "_g", None):
-            self._lib.mi355rec_mf_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("set_profiling", int(max_timed_launches))
 
 
 class _MatrixFactorizationLogic:

@@ -43,8 +43,9 @@ def check_random_state(seed):
     raise ValueError("%r cannot be used to seed a numpy.random.RandomState instance" % seed)
 
 
-class PureSVD_MI355X_Steps:
+class PureSVD_MI355X_Steps(N.Handle):
     """The URM in both layouts and two float32 blocks on the device: side 0 is (n_users, r), side 1 is (n_items, r)."""
+    _PREFIX = "mi355rec_svd"
 
     def __init__(self, URM_train, r):
         X = sps.csr_matrix(URM_train, dtype=np.float32)
@@ -54,10 +55,8 @@ class PureSVD_MI355X_Steps:
         self.n_users, self.n_items = X.shape
         self.r = int(r)
         self.nnz = int(X.nnz)
-        lib = N.load()
-        self._h = C.c_void_p()
         arrays = (N.as_i32(X.indptr), N.as_i32(X.indices), N.as_f32(X.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
-        N.check(lib.mi355rec_svd_create(C.byref(self._h), self.n_users, self.n_items, self.r, *[N.ptr(a) for a in arrays]))
+        self._create(self.n_users, self.n_items, self.r, *[N.ptr(a) for a in arrays])
 
     def rows_of(self, side):
         return self.n_items if side else self.n_users
@@ -66,53 +65,37 @@ class PureSVD_MI355X_Steps:
         X = N.as_f32(X)
         if side not in (0, 1) or X.shape != (self.rows_of(side), self.r):
             raise ValueError("block of side %r must be %d x %d, got %r" % (side, self.rows_of(side) if side in (0, 1) else -1, self.r, X.shape))
-        N.check(N.load().mi355rec_svd_set_block(self._h, side, N.ptr(X)))
+        self._call("set_block", side, N.ptr(X))
 
     def get_block(self, side):
         if side not in (0, 1):
             raise ValueError("side %r: 0 (users) or 1 (items)" % (side,))
         X = np.empty((self.rows_of(side), self.r), np.float32)
-        N.check(N.load().mi355rec_svd_get_block(self._h, side, N.ptr(X)))
+        self._call("get_block", side, N.ptr(X))
         return X
 
     def product(self, dst_side):
         """dst_side 0: block[0] = URM . block[1]; dst_side 1: block[1] = URM^T . block[0]."""
-        N.check(N.load().mi355rec_svd_product(self._h, int(dst_side)))
+        self._call("product", int(dst_side))
 
     def gram(self, side):
         G = np.empty((self.r, self.r), np.float64)
-        N.check(N.load().mi355rec_svd_gram(self._h, int(side), N.ptr(G)))
+        self._call("gram", int(side), N.ptr(G))
         return G
 
     def apply(self, side, T):
         T = N.as_f32(T)
         if T.shape != (self.r, self.r):
             raise ValueError("the matrix of an apply must be %d x %d, got %r" % (self.r, self.r, T.shape))
-        N.check(N.load().mi355rec_svd_apply(self._h, int(side), N.ptr(T)))
-
-    def stats(self):
-        s = N.Stats()
-        N.check(N.load().mi355rec_svd_get_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        self._call("apply", int(side), N.ptr(T))
 
     def fit_info(self):
         ms = [C.c_double() for _ in range(3)]
         v = [C.c_int64() for _ in range(5)]
         ones = C.c_int32()
-        N.check(N.load().mi355rec_svd_fit_info(self._h, *[C.byref(x) for x in ms + v], C.byref(ones)))
+        self._call("fit_info", *[C.byref(x) for x in ms + v], C.byref(ones))
         return {"product_ms": ms[0].value, "gram_ms": ms[1].value, "apply_ms": ms[2].value, "launches": v[0].value, "calls": v[1].value,
                 "create_bytes": v[2].value, "h2d_bytes": v[3].value, "d2h_bytes": v[4].value, "all_ones": bool(ones.value)}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            N.load().mi355rec_svd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _inverse_cholesky_factor(G):

@@ -7,14 +7,28 @@ reference's evaluation loop asks on every validation (Base/Evaluation/Evaluator.
 `GpuScoringMixin` plugs it under `recommend()` of a BaseMatrixFactorizationRecommender without changing its signature;
 `_compute_item_score` itself is left untouched (host NumPy), so either path can be checked against the other.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _native as N
 
 
-class MI355XScorer:
+class _Scorer(N.Handle):
+    """What the two scorers share: recommend() over mi355rec_<kind>_recommend; n_items is the width of a score row."""
+
+    def recommend(self, user_id_array, cutoff, remove_seen=True, allowed_items=None, return_scores=False):
+        """ranked: int32 (n, cutoff) with -1 padding; scores: float32 (n, n_items) with -inf for filtered items."""
+        users = N.as_i32(np.atleast_1d(user_id_array))
+        cutoff = int(min(cutoff, self.n_items))
+        ranked = np.empty((len(users), cutoff), np.int32)
+        scores = np.empty((len(users), self.n_items), np.float32) if return_scores else None
+        mask = None if allowed_items is None else np.ascontiguousarray(allowed_items, dtype=np.uint8)
+        self._call("recommend", N.ptr(users), len(users), cutoff, int(bool(remove_seen)), N.ptr(mask), N.ptr(ranked), N.ptr(scores))
+        return ranked, scores
+
+
+class MI355XScorer(_Scorer):
+    _PREFIX = "mi355rec_scorer"
+
     def __init__(self, USER_factors, ITEM_factors, URM_seen, USER_bias=None, ITEM_bias=None, GLOBAL_bias=0.0):
         U, V = N.as_f32(USER_factors), N.as_f32(ITEM_factors)
         assert U.shape[1] == V.shape[1], "User and Item factors have inconsistent shape"
@@ -25,45 +39,15 @@ class MI355XScorer:
         indptr, indices = N.as_i32(seen.indptr), N.as_i32(seen.indices)
         bu = N.as_f32(USER_bias) if self.use_bias else None
         bi = N.as_f32(ITEM_bias) if self.use_bias else None
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_scorer_create(C.byref(self._h), self.n_users, self.n_items, self.n_factors, N.ptr(U), N.ptr(V),
-                                                 int(self.use_bias), N.ptr(bu), N.ptr(bi), float(np.asarray(GLOBAL_bias)),
-                                                 N.ptr(indptr), N.ptr(indices)))
+        self._create(self.n_users, self.n_items, self.n_factors, N.ptr(U), N.ptr(V), int(self.use_bias), N.ptr(bu), N.ptr(bi),
+                     float(np.asarray(GLOBAL_bias)), N.ptr(indptr), N.ptr(indices))
 
     def update(self, USER_factors, ITEM_factors, USER_bias=None, ITEM_bias=None, GLOBAL_bias=0.0):
         U, V = N.as_f32(USER_factors), N.as_f32(ITEM_factors)
         assert U.shape == (self.n_users, self.n_factors) and V.shape == (self.n_items, self.n_factors)
         bu = N.as_f32(USER_bias) if self.use_bias else None
         bi = N.as_f32(ITEM_bias) if self.use_bias else None
-        N.check(self._lib.mi355rec_scorer_update(self._h, N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), float(np.asarray(GLOBAL_bias))))
-
-    def recommend(self, user_id_array, cutoff, remove_seen=True, allowed_items=None, return_scores=False):
-        """ranked: int32 (n, cutoff) with -1 padding; scores: float32 (n, n_items) with -inf for filtered items."""
-        users = N.as_i32(np.atleast_1d(user_id_array))
-        cutoff = int(min(cutoff, self.n_items))
-        ranked = np.empty((len(users), cutoff), np.int32)
-        scores = np.empty((len(users), self.n_items), np.float32) if return_scores else None
-        mask = None if allowed_items is None else np.ascontiguousarray(allowed_items, dtype=np.uint8)
-        N.check(self._lib.mi355rec_scorer_recommend(self._h, N.ptr(users), len(users), cutoff, int(bool(remove_seen)),
-                                                    N.ptr(mask), N.ptr(ranked), N.ptr(scores)))
-        return ranked, scores
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_scorer_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_scorer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("update", N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), float(np.asarray(GLOBAL_bias)))
 
 
 def _fingerprint(array):
@@ -92,7 +76,45 @@ def allowed_items(recommender, items_to_compute=None, remove_top_pop_flag=False,
     return allowed
 
 
-class GpuScoringMixin:
+def ranked_lists(ranked):
+    """(n, cutoff) ranked array -> n lists of item ids without the -1 that pads rows whose user has fewer than `cutoff` admissible
+    items: rare -- one C-level tolist() otherwise, a tenth of the per-row masks' time on blocks of 1000 users."""
+    return ranked.tolist() if ranked.size and int(ranked.min()) >= 0 else [row[row >= 0].tolist() for row in ranked]
+
+
+class _ScoringMixin:
+    """What the two mixins below share: recommend() of BaseRecommender (same signature, same return values) over the ranked array of
+    a device scorer, and dropping that scorer.  A subclass names the attributes that cache its scorer and what it was built from
+    (`_SCORER_ATTRS`) and builds or re-uses the scorer in `_scorer_for(users)`."""
+    _SCORER_ATTRS = None
+
+    def invalidate_scorer(self):
+        """Forget the device copy of the model: the next recommend() uploads it again.  The caches notice REPLACED arrays (identity)
+        and wholesale in-place changes (a strided 256-element fingerprint -- an optimiser step moves practically every cell); code
+        that edits a few rows of a factor matrix in place (folding in cold users, say) must call this.  The package's own training
+        loops call it from _prepare_model_for_validation."""
+        scorer_attr, src_attr = self._SCORER_ATTRS
+        setattr(self, src_attr, None)
+        scorer = getattr(self, scorer_attr)
+        if scorer is not None:
+            scorer.close()
+            setattr(self, scorer_attr, None)
+
+    def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None, remove_top_pop_flag=False,
+                  remove_custom_items_flag=False, return_scores=False):
+        single_user = np.isscalar(user_id_array)
+        users = np.atleast_1d(user_id_array)
+        if cutoff is None:
+            cutoff = self.URM_train.shape[1] - 1
+        allowed = allowed_items(self, items_to_compute, remove_top_pop_flag, remove_custom_items_flag)
+        ranked, scores = self._scorer_for(users).recommend(users, cutoff, remove_seen_flag, allowed, return_scores)
+        ranking_list = ranked_lists(ranked)
+        if single_user:
+            ranking_list = ranking_list[0]
+        return (ranking_list, scores) if return_scores else ranking_list
+
+
+class GpuScoringMixin(_ScoringMixin):
     """recommend() of BaseRecommender (same signature, same return values) served by MI355XScorer.  The scorer is
     (re)built lazily from the host attributes USER_factors / ITEM_factors[/biases] and URM_train, so it follows
     early-stopping's _prepare_model_for_validation / best-model swaps and set_URM_train automatically.  The cache holds
@@ -100,16 +122,7 @@ class GpuScoringMixin:
     by its successor) plus a content fingerprint (in-place edits)."""
     _scorer = None
     _scorer_src = None
-
-    def invalidate_scorer(self):
-        """Forget the device copy of the model: the next recommend() uploads USER_factors / ITEM_factors again.  The cache notices
-        REPLACED arrays (identity) and wholesale in-place changes (a strided 256-element fingerprint -- an optimiser step moves
-        practically every cell); code that edits a few rows of a factor matrix in place (folding in cold users, say) must call
-        this.  The package's own training loops call it from _prepare_model_for_validation."""
-        self._scorer_src = None
-        if self._scorer is not None:
-            self._scorer.close()
-            self._scorer = None
+    _SCORER_ATTRS = ("_scorer", "_scorer_src")
 
     def _scorer_sources(self):
         src = [self.USER_factors, self.ITEM_factors]
@@ -133,29 +146,18 @@ class GpuScoringMixin:
         self._scorer_src = {"src": src, "prints": prints, "urm": self.URM_train}
         return self._scorer
 
-    def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None, remove_top_pop_flag=False,
-                  remove_custom_items_flag=False, return_scores=False):
-        single_user = np.isscalar(user_id_array)
-        users = np.atleast_1d(user_id_array)
-        if cutoff is None:
-            cutoff = self.URM_train.shape[1] - 1
-        allowed = allowed_items(self, items_to_compute, remove_top_pop_flag, remove_custom_items_flag)
+    def _scorer_for(self, users):
         scorer = self._get_scorer()
         assert scorer.n_users > np.max(users), \
             "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
                 self.RECOMMENDER_NAME, scorer.n_users, np.max(users))
-        ranked, scores = scorer.recommend(users, cutoff, remove_seen_flag, allowed, return_scores)
-        # (-1 pads rows whose user has fewer than `cutoff` admissible items: rare -- one C-level tolist() otherwise, a tenth of the
-        # per-row masks' time on blocks of 1000 users)
-        ranking_list = ranked.tolist() if ranked.size and int(ranked.min()) >= 0 else [row[row >= 0].tolist() for row in ranked]
-        if single_user:
-            ranking_list = ranking_list[0]
-        return (ranking_list, scores) if return_scores else ranking_list
+        return scorer
 
 
-class MI355XSparseScorer:
+class MI355XSparseScorer(_Scorer):
     """scores[u] = A[u, :] . B for sparse A, B (ItemKNN / SLIM: A = URM_train, B = W_sparse; UserKNN: A = W_sparse,
     B = URM_train), filtered and ranked on the device like MI355XScorer."""
+    _PREFIX = "mi355rec_spscorer"
 
     def __init__(self, A, B, URM_seen):
         A, B, seen = A.tocsr(), B.tocsr(), URM_seen.tocsr()
@@ -163,51 +165,17 @@ class MI355XSparseScorer:
         self.n_users, self.n_items = A.shape[0], B.shape[1]
         arrs = [N.as_i32(A.indptr), N.as_i32(A.indices), N.as_f32(A.data), N.as_i32(B.indptr), N.as_i32(B.indices),
                 N.as_f32(B.data), N.as_i32(seen.indptr), N.as_i32(seen.indices)]
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_spscorer_create(C.byref(self._h), A.shape[0], A.shape[1], B.shape[1], *[N.ptr(a) for a in arrs]))
-
-    def recommend(self, user_id_array, cutoff, remove_seen=True, allowed_items=None, return_scores=False):
-        users = N.as_i32(np.atleast_1d(user_id_array))
-        cutoff = int(min(cutoff, self.n_items))
-        ranked = np.empty((len(users), cutoff), np.int32)
-        scores = np.empty((len(users), self.n_items), np.float32) if return_scores else None
-        mask = None if allowed_items is None else np.ascontiguousarray(allowed_items, dtype=np.uint8)
-        N.check(self._lib.mi355rec_spscorer_recommend(self._h, N.ptr(users), len(users), cutoff, int(bool(remove_seen)),
-                                                      N.ptr(mask), N.ptr(ranked), N.ptr(scores)))
-        return ranked, scores
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_spscorer_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_spscorer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(A.shape[0], A.shape[1], B.shape[1], *[N.ptr(a) for a in arrs])
 
 
-class GpuSimilarityScoringMixin:
+class GpuSimilarityScoringMixin(_ScoringMixin):
     """recommend() for BaseItemSimilarityMatrixRecommender / BaseUserSimilarityMatrixRecommender subclasses, served by
     MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  The scorer is rebuilt whenever W_sparse or
     URM_train is replaced (fit, early-stopping validation)."""
     _SCORER_USER_BASED = False
     _sp_scorer = None
     _sp_scorer_src = None
-
-    def invalidate_scorer(self):
-        """Forget the device copy of the model (see GpuScoringMixin.invalidate_scorer): the next recommend() uploads it again."""
-        self._sp_scorer_src = None
-        if self._sp_scorer is not None:
-            self._sp_scorer.close()
-            self._sp_scorer = None
+    _SCORER_ATTRS = ("_sp_scorer", "_sp_scorer_src")
 
     def _get_sparse_scorer(self):
         # strong references + identity (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of
@@ -223,17 +191,5 @@ class GpuSimilarityScoringMixin:
             self._sp_scorer_src = {"W": W, "urm": self.URM_train, "print": print_now}
         return self._sp_scorer
 
-    def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None, remove_top_pop_flag=False,
-                  remove_custom_items_flag=False, return_scores=False):
-        single_user = np.isscalar(user_id_array)
-        users = np.atleast_1d(user_id_array)
-        if cutoff is None:
-            cutoff = self.URM_train.shape[1] - 1
-        allowed = allowed_items(self, items_to_compute, remove_top_pop_flag, remove_custom_items_flag)
-        ranked, scores = self._get_sparse_scorer().recommend(users, cutoff, remove_seen_flag, allowed, return_scores)
-        # (-1 pads rows whose user has fewer than `cutoff` admissible items: rare -- one C-level tolist() otherwise, a tenth of the
-        # per-row masks' time on blocks of 1000 users)
-        ranking_list = ranked.tolist() if ranked.size and int(ranked.min()) >= 0 else [row[row >= 0].tolist() for row in ranked]
-        if single_user:
-            ranking_list = ranking_list[0]
-        return (ranking_list, scores) if return_scores else ranking_list
+    def _scorer_for(self, users):
+        return self._get_sparse_scorer()

@@ -29,8 +29,9 @@ def slabs_to_csr(nbr_idx, nbr_val, start_col, n_columns):
     return W.tocsr()
 
 
-class Compute_Similarity_MI355X:
+class Compute_Similarity_MI355X(N.Handle):
     """Drop-in for Compute_Similarity_Cython backed by the gfx950 kernels."""
+    _PREFIX = "mi355rec_sim"
 
     SIMILARITY_VALUES = ("cosine", "pearson", "adjusted", "asymmetric", "jaccard", "tanimoto", "dice", "tversky")
 
@@ -78,27 +79,13 @@ class Compute_Similarity_MI355X:
                           norm_sum_order, 0)
         assert weighting_documents in ("columns", "rows")
         self._weighted_structure = (csr.indptr, csr.indices, csr.shape) if feature_weighting != "none" else None
-        self._lib = N.load()
-        self._h = C.c_void_p()
         if resident is not None:
             if not resident.matches(csr):
                 raise ValueError("Compute_Similarity_MI355X: `resident` does not hold this dataMatrix (shape, nnz or contents differ)")
-            N.check(self._lib.mi355rec_sim_create_resident(C.byref(self._h), C.byref(cfg), self.n_rows, self.n_columns,
-                                                           resident.indptr.ptr, resident.indices.ptr, resident.data.ptr, N.ptr(rw)))
+            self._create(C.byref(cfg), self.n_rows, self.n_columns, resident.indptr.ptr, resident.indices.ptr, resident.data.ptr, N.ptr(rw),
+                         entry="create_resident")
         else:
-            N.check(self._lib.mi355rec_sim_create(C.byref(self._h), C.byref(cfg), self.n_rows, self.n_columns,
-                                                  N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(rw)))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_sim_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._create(C.byref(cfg), self.n_rows, self.n_columns, N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(rw))
 
     def weighted_matrix(self):
         """The BM25 / TF-IDF re-weighted dataMatrix (csr, float32), computed on the device by the constructor."""
@@ -106,7 +93,7 @@ class Compute_Similarity_MI355X:
             raise ValueError("Compute_Similarity_MI355X was created with feature_weighting='none'")
         indptr, indices, shape = self._weighted_structure
         data = np.empty(len(indices), np.float32)
-        N.check(self._lib.mi355rec_sim_get_weighted_values(self._h, N.ptr(data)))
+        self._call("get_weighted_values", N.ptr(data))
         return sps.csr_matrix((data, indices.copy(), indptr.copy()), shape=shape)
 
     def _range(self, start_col, end_col):
@@ -123,69 +110,64 @@ class Compute_Similarity_MI355X:
         s, e = self._range(start_col, end_col)
         idx = np.empty((e - s, self.TopK), dtype=np.int32)
         val = np.empty((e - s, self.TopK), dtype=np.float32)
-        N.check(self._lib.mi355rec_sim_compute(self._h, s, e, N.ptr(idx), N.ptr(val)))
+        self._call("compute", s, e, N.ptr(idx), N.ptr(val))
         return idx, val, s
 
     def compute_slabs_device(self, start_col, end_col, d_idx_ptr, d_val_ptr):
         """Asynchronous variant writing into device buffers (data_ptr() of int32 / float32 tensors)."""
         s, e = self._range(start_col, end_col)
-        N.check(self._lib.mi355rec_sim_compute_device(self._h, s, e, C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr)))
+        self._call("compute_device", s, e, C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr))
         return s, e
 
     def compute_part_device(self, part, n_parts, d_idx_ptr, d_val_ptr):
         """Asynchronous build of interleaved part `part` of `n_parts` (equal column counts and equal cost per part) into device
         slabs of ceil(n_columns / n_parts) rows; row q holds column part_columns(part, n_parts)[q]."""
-        N.check(self._lib.mi355rec_sim_compute_part_device(self._h, int(part), int(n_parts), C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr)))
+        self._call("compute_part_device", int(part), int(n_parts), C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr))
 
     def compute_part_chunk_device(self, part, n_parts, slot_first, slot_count, d_idx_ptr, d_val_ptr):
         """Rows [slot_first, slot_first + slot_count) of interleaved part `part` only, into rows 0 .. slot_count - 1 of the slabs."""
-        N.check(self._lib.mi355rec_sim_compute_part_chunk_device(self._h, int(part), int(n_parts), int(slot_first), int(slot_count),
-                                                                 C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr)))
+        self._call("compute_part_chunk_device", int(part), int(n_parts), int(slot_first), int(slot_count), C.c_void_p(d_idx_ptr),
+                   C.c_void_p(d_val_ptr))
 
     def pack_slab_device(self, d_idx_ptr, d_val_ptr, n_cells, d_packed_ptr):
         """(idx, val) device slabs of n_cells cells -> the 6-byte exchange cells (values, then 16-bit ids); asynchronous on the handle's stream."""
-        N.check(self._lib.mi355rec_sim_pack_slab_device(self._h, C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr), int(n_cells), C.c_void_p(d_packed_ptr)))
+        self._call("pack_slab_device", C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr), int(n_cells), C.c_void_p(d_packed_ptr))
 
     def unpack_slab_device(self, d_packed_ptr, n_cells, d_idx_ptr, d_val_ptr):
-        N.check(self._lib.mi355rec_sim_unpack_slab_device(self._h, C.c_void_p(d_packed_ptr), int(n_cells), C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr)))
+        self._call("unpack_slab_device", C.c_void_p(d_packed_ptr), int(n_cells), C.c_void_p(d_idx_ptr), C.c_void_p(d_val_ptr))
 
     def part_columns(self, part, n_parts):
         n = C.c_int32()
-        N.check(self._lib.mi355rec_sim_part_columns(self._h, int(part), int(n_parts), None, C.byref(n)))
+        self._call("part_columns", int(part), int(n_parts), None, C.byref(n))
         cols = np.empty(n.value, np.int32)
-        N.check(self._lib.mi355rec_sim_part_columns(self._h, int(part), int(n_parts), N.ptr(cols), C.byref(n)))
+        self._call("part_columns", int(part), int(n_parts), N.ptr(cols), C.byref(n))
         return cols
 
     def synchronize(self):
-        N.check(self._lib.mi355rec_sim_sync(self._h))
+        self._call("sync")
 
     def column_costs(self):
         cost = np.empty(self.n_columns, dtype=np.int64)
-        N.check(self._lib.mi355rec_sim_column_costs(self._h, N.ptr(cost)))
+        self._call("column_costs", N.ptr(cost))
         return cost
 
     def schedule_info(self):
         """(work items, split columns, parts) of the last compute call."""
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
-        N.check(self._lib.mi355rec_sim_schedule_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._call("schedule_info", C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
     def accumulator_info(self):
         """("uint32" | "int64-fixed" | "float64" | "int32-exact", scale): type of the in-LDS column accumulator (diagnostics)."""
         kind, scale = C.c_int32(), C.c_double()
-        N.check(self._lib.mi355rec_sim_accumulator_info(self._h, C.byref(kind), C.byref(scale)))
+        self._call("accumulator_info", C.byref(kind), C.byref(scale))
         return ("uint32", "int64-fixed", "float64", "int32-exact")[kind.value], scale.value
 
     def selection_info(self):
         """(columns selected threshold-first, their candidates in total, fall-backs to the full selection) of the last compute call."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-        N.check(self._lib.mi355rec_sim_selection_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._call("selection_info", C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
-
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_sim_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
 
     def compute_similarity(self, start_col=None, end_col=None):
         if self.TopK == 0:
@@ -193,7 +175,7 @@ class Compute_Similarity_MI355X:
             # the device writes columns [s, e) straight into W (row pitch n_columns): no second n x n array on the host
             W = np.zeros((self.n_columns, self.n_columns), dtype=np.float32) if (s, e) != (0, self.n_columns) else \
                 np.empty((self.n_columns, self.n_columns), dtype=np.float32)
-            N.check(self._lib.mi355rec_sim_compute_dense(self._h, s, e, C.c_void_p(W.ctypes.data + 4 * s), self.n_columns))
+            self._call("compute_dense", s, e, C.c_void_p(W.ctypes.data + 4 * s), self.n_columns)
             return W
         # CSR assembled on the device: SciPy's COO/CSC -> CSR conversion of the result would cost more than the build
         s, e = self._range(start_col, end_col)
@@ -202,7 +184,7 @@ class Compute_Similarity_MI355X:
         indices = np.empty(cap, dtype=np.int32)
         data = np.empty(cap, dtype=np.float32)
         nnz = C.c_int64()
-        N.check(self._lib.mi355rec_sim_compute_csr(self._h, s, e, N.ptr(indptr), N.ptr(indices), N.ptr(data), C.byref(nnz)))
+        self._call("compute_csr", s, e, N.ptr(indptr), N.ptr(indices), N.ptr(data), C.byref(nnz))
         W = sps.csr_matrix((data[:nnz.value], indices[:nnz.value], indptr), shape=(self.n_columns, self.n_columns))
         W.has_sorted_indices = True
         return W

@@ -30,7 +30,9 @@ def rows_slabs_to_csr(nbr_idx, nbr_val, n):
     return sps.csr_matrix((nbr_val[keep].astype(np.float64), nbr_idx[keep], indptr), shape=(n, n))
 
 
-class SLIM_BPR_MI355X_Epoch:
+class SLIM_BPR_MI355X_Epoch(N.Handle):
+    _PREFIX = "mi355rec_slim"
+
     def __init__(self, URM_mask, train_with_sparse_weights=False, final_model_sparse_weights=True, learning_rate=0.01,
                  li_reg=0.0, lj_reg=0.0, batch_size=1, topK=150, symmetric=True, verbose=False, random_seed=None,
                  sgd_mode="adam", gamma=0.995, beta_1=0.9, beta_2=0.999, precision="auto"):
@@ -67,26 +69,12 @@ class SLIM_BPR_MI355X_Epoch:
                            beta_2, seed & (2 ** 64 - 1), N.PRECISION_CODES[precision], int(self.train_with_sparse_weights),
                            int(topK) if topK else 0, 0)
         indptr, indices = N.as_i32(URM_mask.indptr), N.as_i32(URM_mask.indices)
-        self._lib = N.load()
-        self._h = C.c_void_p()
-        N.check(self._lib.mi355rec_slim_create(C.byref(self._h), C.byref(cfg), self.n_users, self.n_items,
-                                               N.ptr(indptr), N.ptr(indices)))
+        self._create(C.byref(cfg), self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices))
 
-    def _dealloc(self):
-        if getattr(self, "_h", None):
-            self._lib.mi355rec_slim_destroy(self._h)
-            self._h = None
-
-    close = _dealloc
-
-    def __del__(self):
-        try:
-            self._dealloc()
-        except Exception:
-            pass
+    _dealloc = N.Handle.close           # the reference's name for it (.pyx:195)
 
     def epochIteration_Cython(self, n_epochs=1):
-        N.check(self._lib.mi355rec_slim_run_epochs(self._h, int(n_epochs)))
+        self._call("run_epochs", int(n_epochs))
         if self.verbose:
             st = self.stats()
             print("Processed {} samples in {:.3f} seconds. BPR loss is {:.2E}. Sample per second: {:.0f}".format(
@@ -95,25 +83,25 @@ class SLIM_BPR_MI355X_Epoch:
 
     def replay_samples(self, user, pos_item, neg_item):
         u, i, j = N.as_i32(user), N.as_i32(pos_item), N.as_i32(neg_item)
-        N.check(self._lib.mi355rec_slim_run_samples(self._h, N.ptr(u), N.ptr(i), N.ptr(j), len(u)))
+        self._call("run_samples", N.ptr(u), N.ptr(i), N.ptr(j), len(u))
 
     def last_epoch_samples(self):
         """(user, pos_item, neg_item) drawn on the device during the last native epoch."""
         n = C.c_int64(0)
-        N.check(self._lib.mi355rec_slim_get_last_samples(self._h, None, None, None, 0, C.byref(n)))
+        self._call("get_last_samples", None, None, None, 0, C.byref(n))
         u = np.empty(n.value, np.int32); i = np.empty(n.value, np.int32); j = np.empty(n.value, np.int32)
-        N.check(self._lib.mi355rec_slim_get_last_samples(self._h, N.ptr(u), N.ptr(i), N.ptr(j), n.value, C.byref(n)))
+        self._call("get_last_samples", N.ptr(u), N.ptr(i), N.ptr(j), n.value, C.byref(n))
         return u, i, j
 
     def get_S_dense(self):
         S = np.empty((self.n_items, self.n_items), np.float32)
-        N.check(self._lib.mi355rec_slim_get_S_dense(self._h, N.ptr(S)))
+        self._call("get_S_dense", N.ptr(S))
         return S
 
     def get_S_slabs(self, topK):
         k = min(int(topK), self.n_items)
         idx = np.empty((self.n_items, k), np.int32); val = np.empty((self.n_items, k), np.float32)
-        N.check(self._lib.mi355rec_slim_get_S_topk(self._h, k, N.ptr(idx), N.ptr(val)))
+        self._call("get_S_topk", k, N.ptr(idx), N.ptr(val))
         return idx, val
 
     def selects_rows(self):
@@ -129,7 +117,7 @@ class SLIM_BPR_MI355X_Epoch:
         idx = np.empty((self.n_items, k), np.int32); val = np.empty((self.n_items, k), np.float32)
         indptr = np.empty(self.n_items + 1, np.int32); indices = np.empty(self.n_items * k, np.int32); data = np.empty(self.n_items * k, np.float32)
         nnz = C.c_int64(0)
-        N.check(self._lib.mi355rec_slim_get_W_csr(self._h, k, N.ptr(idx), N.ptr(val), N.ptr(indptr), N.ptr(indices), N.ptr(data), C.byref(nnz)))
+        self._call("get_W_csr", k, N.ptr(idx), N.ptr(val), N.ptr(indptr), N.ptr(indices), N.ptr(data), C.byref(nnz))
         W = sps.csr_matrix((data[:nnz.value], indices[:nnz.value], indptr), shape=(self.n_items, self.n_items))
         W.has_sorted_indices = True
         return rows_slabs_to_csr(idx, val, self.n_items), W
@@ -142,7 +130,7 @@ class SLIM_BPR_MI355X_Epoch:
             if not self.topK:
                 return sps.csr_matrix(self.get_S_dense().astype(np.float64))
             idx = np.empty((self.n_items, int(self.topK)), np.int32); val = np.empty((self.n_items, int(self.topK)), np.float32)
-            N.check(self._lib.mi355rec_slim_get_S_sparse(self._h, N.ptr(idx), N.ptr(val)))
+            self._call("get_S_sparse", N.ptr(idx), N.ptr(val))
             return rows_slabs_to_csr(idx, val, self.n_items)
         if not self.topK:
             S = self.get_S_dense().astype(np.float64)
@@ -152,15 +140,10 @@ class SLIM_BPR_MI355X_Epoch:
         idx, val = self.get_S_slabs(self.topK)
         return rows_slabs_to_csr(idx, val, self.n_items)
 
-    def stats(self):
-        st = N.Stats()
-        N.check(self._lib.mi355rec_slim_get_stats(self._h, C.byref(st)))
-        return st.as_dict()
-
     def schedule_info(self):
         """(rows an owning workgroup kept in LDS, steps that ran on rows in HBM) of the last dense-store launch."""
         a, b = C.c_int32(0), C.c_int32(0)
-        N.check(self._lib.mi355rec_slim_schedule_info(self._h, C.byref(a), C.byref(b)))
+        self._call("schedule_info", C.byref(a), C.byref(b))
         return a.value, b.value
 
 

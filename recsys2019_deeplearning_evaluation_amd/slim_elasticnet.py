@@ -36,8 +36,9 @@ def _biggest_unit(seconds):
     return value, unit
 
 
-class SLIMElasticNet_MI355X_Fit:
+class SLIMElasticNet_MI355X_Fit(N.Handle):
     """One Gram matrix on the device and fits of item ranges against it (multi-GPU sharding would hand each rank a range)."""
+    _PREFIX = "mi355rec_slimen"
 
     def __init__(self, URM_train):
         X = sps.csr_matrix(URM_train, dtype=np.float32)
@@ -45,48 +46,29 @@ class SLIMElasticNet_MI355X_Fit:
         Xc = sps.csc_matrix(X)
         Xc.sort_indices()
         self.n_users, self.n_items = X.shape
-        lib = N.load()
-        self._h = C.c_void_p()
         arrays = (N.as_i32(X.indptr), N.as_i32(X.indices), N.as_f32(X.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
-        N.check(lib.mi355rec_slimen_create(C.byref(self._h), self.n_users, self.n_items, *[N.ptr(a) for a in arrays]))
+        self._create(self.n_users, self.n_items, *[N.ptr(a) for a in arrays])
 
     def fit_range(self, start, end, seeds, alpha, l1_ratio, positive_only, topK, max_iter=100, tol=1e-4):
         """Fits targets [start, end); returns (rows, values, counts, n_iter, converged) with rows / values (end - start, slots).
         topK = -1 keeps every nonzero coefficient of each target instead of the reference's min(nnz - 1, topK)."""
         seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
         assert len(seeds) == end - start
-        lib = N.load()
-        N.check(lib.mi355rec_slimen_fit(self._h, int(start), int(end), N.ptr(seeds), float(alpha), float(l1_ratio), int(bool(positive_only)),
-                                        int(topK), int(max_iter), float(tol)))
+        self._call("fit", int(start), int(end), N.ptr(seeds), float(alpha), float(l1_ratio), int(bool(positive_only)), int(topK), int(max_iter),
+                   float(tol))
         n = end - start
         slots = max(1, self.n_items - 1 if topK < 0 else min(int(topK), self.n_items - 1))
         counts, n_iter, conv = (np.zeros(n, np.int32) for _ in range(3))
         rows, values = np.zeros((n, slots), np.int32), np.zeros((n, slots), np.float32)
-        N.check(lib.mi355rec_slimen_get(self._h, N.ptr(counts), N.ptr(n_iter), N.ptr(conv), N.ptr(rows), N.ptr(values), slots))
+        self._call("get", N.ptr(counts), N.ptr(n_iter), N.ptr(conv), N.ptr(rows), N.ptr(values), slots)
         return rows, values, counts, n_iter, conv.astype(bool)
-
-    def stats(self):
-        s = N.Stats()
-        N.check(N.load().mi355rec_slimen_get_stats(self._h, C.byref(s)))
-        return s.as_dict()
 
     def fit_info(self):
         v = [C.c_int64() for _ in range(4)]
         lds, gram_ms = C.c_int32(), C.c_double()
-        N.check(N.load().mi355rec_slimen_fit_info(self._h, *[C.byref(x) for x in v], C.byref(lds), C.byref(gram_ms)))
+        self._call("fit_info", *[C.byref(x) for x in v], C.byref(lds), C.byref(gram_ms))
         return {"changes": v[0].value, "sweeps": v[1].value, "steps": v[2].value, "gap_tests": v[3].value, "h_in_lds": bool(lds.value),
                 "gram_ms": gram_ms.value}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            N.load().mi355rec_slimen_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def slots_to_csr(rows, values, counts, start, n_items):

@@ -18,9 +18,9 @@ for tag in ("graph", ):
     m.epochIteration_Cython(n_ep); st = m.stats()
     print(tag, "epoch ms", st["call_ms"] / n_ep, "samples/s %.1fM" % (st["n_units"] / st["call_ms"] / 1e3), "us per mini-batch %.2f" % (st["call_ms"] * 1e3 / st["n_launches"]))
 n = C.c_int64(0)
-N.check(m._lib.mi355rec_mf_get_phase_ticks(m._h, None, 0, C.byref(n)))
+m._call("get_phase_ticks", None, 0, C.byref(n))
 t = np.zeros(n.value, np.uint64)
-N.check(m._lib.mi355rec_mf_get_phase_ticks(m._h, N.ptr(t), n.value, C.byref(n)))
+m._call("get_phase_ticks", N.ptr(t), n.value, C.byref(n))
 t = t.reshape(-1, 8).astype(np.int64)
 act = t[:, 5] > 0
 print("active waves", act.sum(), "of", len(t))
