@@ -195,7 +195,7 @@ int mi355rec_sim_schedule_info(mi355rec_sim_t h, int32_t *n_items, int32_t *n_sp
  * environment at create time).  Diagnostics for the parity tests. */
 int mi355rec_sim_accumulator_info(mi355rec_sim_t h, int32_t *kind, double *fixed_scale);
 /* Selection path of the last compute call (diagnostics for the parity tests): columns whose top-K was found threshold-first
- * (per-thread maxima -> K-th largest maximum -> exact division of the survivors only; csrc/sim.hip), the survivors those columns
+ * (per-thread maxima -> K-th largest maximum -> exact division of the survivors only; csrc/sim_kernels.cuh), the survivors those columns
  * ranked in total, and columns that went back to the full normalise + radix select after their scan (more survivors than the
  * candidate buffer holds).  Columns with fewer than topK positive cells, accumulator tiles, 8-byte cells, topK == 0 and the
  * Euclidean cell map always take the full path and are counted nowhere.  MI355REC_SIM_FAST_TOPK=0 switches the first path off. */

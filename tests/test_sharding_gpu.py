@@ -129,7 +129,7 @@ def test_packed_exchange_cells_on_the_device(gpu):
 
 def test_parts_at_ml20m_shape_with_heavy_columns_routed_to_the_32_bit_launch(gpu, monkeypatch):
     """At the ML-20M shape the heavy columns of an 8-way part are 60 % of its pair-adds: the packed-counts call hands them to the 32-bit launch
-    behind it (sim.hip, run_columns_lds: MI355REC_SIM_PACKED_DEMOTE).  Parts 0 and 7 built with that rule (the default), with it forced
+    behind it (sim_plan.h, plan_columns: MI355REC_SIM_PACKED_DEMOTE).  Parts 0 and 7 built with that rule (the default), with it forced
     off, and without the packed kernel at all are identical cell for cell -- whole and in the pieces the sharded build cuts them into --
     and the schedule shows that the rule fired (fewer split columns in the packed call); the whole-shape build does not use it."""
     import numpy as np
