@@ -447,6 +447,51 @@ int mi355rec_svd_fit_info(mi355rec_svd_t h, double *product_ms, double *gram_ms,
 void mi355rec_svd_destroy(mi355rec_svd_t h);
 
 /* ------------------------------------------------------------------------------------------------------
+ * NMF  (MatrixFactorization/NMFRecommender.py:58-71: sklearn.decomposition.NMF of URM_train, then its transform) -- the device steps of
+ * the coordinate-descent and multiplicative-update solvers; the iteration loop, the permutations and the stop rule run on the host
+ * 
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_nmf *mi355rec_nmf_t;
+
+/* URM_train (n_users x n_items) in both layouts, CSR and CSC, float32 values >= 0, indices inside the matrix; k = number of
+ * components.  Resident: side 0 = W (n_users x k) and side 1 = Ht = H^T (n_items x k), float32 row-major, zero after create, and one
+ * value buffer of nnz floats per layout.  k outside [1, 4096], pointers that decrease, indices outside the matrix and negative
+ * values are MI355REC_E_INVALID before the device is touched. */
+int mi355rec_nmf_create(mi355rec_nmf_t *out, int32_t n_users, int32_t n_items, int32_t k, const int32_t *row_ptr, const int32_t *row_idx,
+                        const float *row_val, const int32_t *col_ptr, const int32_t *col_idx, const float *col_val);
+/* Upload / download of the block of a side (rows_of(side) x k floats); fill_block sets every cell to `value` (>= 0) on the device. */
+int mi355rec_nmf_set_block(mi355rec_nmf_t h, int32_t side, const float *X);
+int mi355rec_nmf_get_block(mi355rec_nmf_t h, int32_t side, float *X);
+int mi355rec_nmf_fill_block(mi355rec_nmf_t h, int32_t side, float value);
+/* One half-sweep of coordinate descent on block[side], the other block fixed (sklearn's _update_cdnmf_fast): for t in the order of
+ * `permutation` (k entries, a permutation of 0 .. k-1, else MI355REC_E_INVALID) and every row i, grad = block[i] . G[t] - P[i][t],
+ * block[i][t] = max(block[i][t] - grad / G[t][t], 0) where G[t][t] != 0; G = other^T other, P = URM . other (side 0) or URM^T . other
+ * (side 1).  reuse = 1 keeps the G and P of the previous frobenius step on the same side (the other block has not changed; otherwise
+ * MI355REC_E_INVALID).  The violation, sum of |projected gradient| in float64 in a fixed order, is added to a device total;
+ * `violation` (nullable) receives that total and resets it, so the two half-sweeps of an iteration cost one 8-byte download. */
+int mi355rec_nmf_cd_sweep(mi355rec_nmf_t h, int32_t side, const int32_t *permutation, int32_t reuse, double *violation);
+/* One multiplicative update of block[side] (sklearn's _multiplicative_update_w / _h).  loss 0, frobenius: block *= P / (block . G), a
+ * zero denominator replaced by float32 eps.  loss 1, Kullback-Leibler: q = x / max(W[i] . Ht[c], eps) per cell of the side's layout,
+ * block *= (q-weighted product with the other block) / (column sums of the other block); a zero sum is float32 eps under W and 1
+ * under Ht, and entries of Ht below float64 eps become 0.  reuse = 1 keeps G and P (frobenius) or the column sums (Kullback-Leibler)
+ * of the previous step on the same side and loss.  Another loss is MI355REC_E_INVALID. */
+int mi355rec_nmf_mu_step(mi355rec_nmf_t h, int32_t side, int32_t loss, int32_t reuse);
+/* sklearn's _beta_divergence(X, W, H) in float64 sums of a fixed order.  loss 0: (|X|^2 + tr((W^T W)(H H^T)) - 2 sum (X H^T) o W) / 2;
+ * loss 1: sum x log(x / max(wh, eps)) over the cells with x > eps + (sum W)(sum H) - sum x. */
+int mi355rec_nmf_divergence(mi355rec_nmf_t h, int32_t loss, double *divergence);
+/* Timing of the last fill_block / cd_sweep / mu_step / divergence call: call_ms = all its kernels, kernel_ms = its sweep, element-wise
+ * pass or SDDMM. */
+int mi355rec_nmf_get_stats(mi355rec_nmf_t h, mi355rec_stats *stats);
+/* Totals since create.  phase_ms[6]: device milliseconds of the sparse products, the GEMMs, the sweeps, the element-wise passes,
+ * the SDDMMs and the reductions (Gram, column sums, dot products, partial sums); kernel launches; calls of the entry points above;
+ * bytes uploaded by create (the URM and its piece tables); host -> device and device -> host bytes since; all_ones = 1 when the URM
+ * holds only ones. */
+int mi355rec_nmf_fit_info(mi355rec_nmf_t h, double *phase_ms, int64_t *launches, int64_t *calls, int64_t *create_bytes, int64_t *h2d_bytes,
+                          int64_t *d2h_bytes, int32_t *all_ones);
+void mi355rec_nmf_destroy(mi355rec_nmf_t h);
+
+/* ------------------------------------------------------------------------------------------------------
  * Scoring + ranking of factor models  (Base/BaseMatrixFactorizationRecommender.py:38
  * _compute_item_score and the filter/rank half of Base/BaseRecommender.py:131 recommend)
  * ---------------------------------------------------------------------------------------------------- */

@@ -2,7 +2,7 @@
 MaurizioFD/RecSys2019_DeepLearning_Evaluation, behind the reference's own recommender surface.
 
 Hot path only: Compute_Similarity (ItemKNN build), BPR-MF / FunkSVD SGD epochs, SLIM-BPR epoch,
-IALS solve step, SLIM ElasticNet coordinate descent, PureSVD's randomized SVD.  Python host code + ctypes C-ABI (include/mi355rec.h) + hand-written HIP kernels (csrc/).
+IALS solve step, SLIM ElasticNet coordinate descent, PureSVD's randomized SVD, NMF's coordinate-descent and multiplicative-update solvers.  Python host code + ctypes C-ABI (include/mi355rec.h) + hand-written HIP kernels (csrc/).
 Nothing here imports torch; torch.distributed is only used by `sharding` for the multi-GPU gather.
 """
 from ._native import ResidentURM  # noqa: F401
@@ -20,6 +20,7 @@ from .ials import IALS_MI355X_Epoch, IALSRecommender  # noqa: F401,E402
 from .slim_elasticnet import SLIMElasticNetRecommender  # noqa: F401,E402
 from .evaluation import EvaluatorHoldout_MI355X  # noqa: F401,E402
 from .pure_svd import PureSVDRecommender, PureSVDItemRecommender  # noqa: F401,E402
+from .nmf import NMFRecommender  # noqa: F401,E402
 
-__all__ = ["ResidentURM", "PureSVDRecommender", "PureSVDItemRecommender", "EvaluatorHoldout_MI355X", "EASE_R_Recommender", "SLIMElasticNetRecommender", "P3alphaRecommender", "RP3betaRecommender", "MI355XScorer", "MI355XSparseScorer", "GpuScoringMixin", "GpuSimilarityScoringMixin", "SLIM_BPR_MI355X_Epoch", "SLIM_BPR_MI355X", "IALS_MI355X_Epoch", "IALSRecommender", "Compute_Similarity", "Compute_Similarity_MI355X", "Compute_Similarity_Euclidean_MI355X", "ItemKNNCFRecommender", "UserKNNCFRecommender",
+__all__ = ["ResidentURM", "PureSVDRecommender", "PureSVDItemRecommender", "NMFRecommender", "EvaluatorHoldout_MI355X", "EASE_R_Recommender", "SLIMElasticNetRecommender", "P3alphaRecommender", "RP3betaRecommender", "MI355XScorer", "MI355XSparseScorer", "GpuScoringMixin", "GpuSimilarityScoringMixin", "SLIM_BPR_MI355X_Epoch", "SLIM_BPR_MI355X", "IALS_MI355X_Epoch", "IALSRecommender", "Compute_Similarity", "Compute_Similarity_MI355X", "Compute_Similarity_Euclidean_MI355X", "ItemKNNCFRecommender", "UserKNNCFRecommender",
            "MatrixFactorization_MI355X_Epoch", "MatrixFactorization_MI355X_Group", "MatrixFactorization_BPR_MI355X", "MatrixFactorization_FunkSVD_MI355X", "MatrixFactorization_AsySVD_MI355X"]

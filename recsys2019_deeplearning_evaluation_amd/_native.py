@@ -154,6 +154,17 @@ SIGNATURES = {
     "mi355rec_svd_fit_info": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_i64),
                                         C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)]),
     "mi355rec_svd_destroy": (None, [_vp]),
+    "mi355rec_nmf_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355rec_nmf_set_block": (C.c_int, [_vp, _i32, _vp]),
+    "mi355rec_nmf_get_block": (C.c_int, [_vp, _i32, _vp]),
+    "mi355rec_nmf_fill_block": (C.c_int, [_vp, _i32, _f32]),
+    "mi355rec_nmf_cd_sweep": (C.c_int, [_vp, _i32, _vp, _i32, C.POINTER(_f64)]),
+    "mi355rec_nmf_mu_step": (C.c_int, [_vp, _i32, _i32, _i32]),
+    "mi355rec_nmf_divergence": (C.c_int, [_vp, _i32, C.POINTER(_f64)]),
+    "mi355rec_nmf_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
+    "mi355rec_nmf_fit_info": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                                        C.POINTER(_i64), C.POINTER(_i32)]),
+    "mi355rec_nmf_destroy": (None, [_vp]),
     "mi355rec_scorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),
     "mi355rec_scorer_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32]),
     "mi355rec_scorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -13,8 +13,10 @@
 //   svd_gram_kernel     G = X^T X in float64 FMAs: 64 x 64 tiles of the upper triangle, a slab of rows per workgroup, the slabs'
 //                       partial tiles added in slab order by svd_gram_reduce_kernel (which mirrors the lower triangle).
 //   block * matrix      X <- X T is score.hip's f32 MFMA GEMM (gemm_rows_enqueue) with the identity as its row gather.
+// The product and the Gram build are also launchers on a caller's stream (svd_product.h): the NMF handle (nmf.hip) runs the same kernels.
 #include "common.h"
 #include "score.h"
+#include "svd_product.h"
 
 #include <algorithm>
 #include <memory>
@@ -164,62 +166,98 @@ __global__ __launch_bounds__(256) void svd_iota_kernel(int *out, int n) {
     if (i < n) out[i] = i;
 }
 
+}  // namespace
+
+// ---- what nmf.hip shares (svd_product.h) ----------------------------------------------------------------------------------------
+namespace mi355rec {
+
 // the kernel gathers block rows by the indices of a layout: pointers that decrease or an index outside the other side are refused
-static void validate_layout(int n, int n_other, const int *ptr, const int *idx) {
+void validate_layout(int n, int n_other, const int *ptr, const int *idx) {
     MI_REQUIRE(ptr[0] == 0, "row pointers do not start at 0");
     for (int i = 0; i < n; ++i) MI_REQUIRE(ptr[i] <= ptr[i + 1], "row pointers decrease at %d", i);
     for (int j = 0, e = ptr[n]; j < e; ++j) MI_REQUIRE(idx[j] >= 0 && idx[j] < n_other, "index %d outside [0, %d)", idx[j], n_other);
 }
 
-// one side of the product: the matrix whose rows are the output rows, and its pieces
-struct Side {
-    int n_rows = 0, n_pieces = 0, n_long = 0, n_slots = 0;
-    DeviceBuffer<int> idx, p_row, p_begin, p_end, p_slot, l_row, l_first, l_count;
-    DeviceBuffer<float> val;
-
-    size_t build(int n, const int *row_ptr, const int *row_idx, const float *row_val, bool ones, hipStream_t s) {
-        n_rows = n;
-        std::vector<int> row, begin, end, slot, lrow, lfirst, lcount;
-        row.reserve(n);
-        for (int i = 0; i < n; ++i) {
-            const int b = row_ptr[i], e = row_ptr[i + 1], len = e - b;
-            const int parts = std::max(1, div_up(len, SPLIT));
-            if (parts > 1) {
-                lrow.push_back(i);
-                lfirst.push_back(n_slots);
-                lcount.push_back(parts);
-            }
-            for (int p = 0; p < parts; ++p) {
-                row.push_back(i);
-                begin.push_back(b + p * SPLIT);
-                end.push_back(std::min(e, b + (p + 1) * SPLIT));
-                slot.push_back(parts > 1 ? n_slots++ : -1);
-            }
+size_t Side::build(int n, const int *row_ptr, const int *row_idx, const float *row_val, bool ones, hipStream_t s) {
+    n_rows = n;
+    std::vector<int> row, begin, end, slot, lrow, lfirst, lcount;
+    row.reserve(n);
+    for (int i = 0; i < n; ++i) {
+        const int b = row_ptr[i], e = row_ptr[i + 1], len = e - b;
+        const int parts = std::max(1, div_up(len, SPLIT));
+        if (parts > 1) {
+            lrow.push_back(i);
+            lfirst.push_back(n_slots);
+            lcount.push_back(parts);
         }
-        n_pieces = (int)row.size();
-        n_long = (int)lrow.size();
-        const size_t nnz = (size_t)row_ptr[n];
-        idx.alloc(std::max<size_t>(nnz, 1));
-        if (nnz) MI_HIP(hipMemcpyAsync(idx.ptr, row_idx, nnz * sizeof(int), hipMemcpyHostToDevice, s));
-        if (!ones) {
-            val.alloc(std::max<size_t>(nnz, 1));
-            if (nnz) MI_HIP(hipMemcpyAsync(val.ptr, row_val, nnz * sizeof(float), hipMemcpyHostToDevice, s));
+        for (int p = 0; p < parts; ++p) {
+            row.push_back(i);
+            begin.push_back(b + p * SPLIT);
+            end.push_back(std::min(e, b + (p + 1) * SPLIT));
+            slot.push_back(parts > 1 ? n_slots++ : -1);
         }
-        p_row.upload(row.data(), row.size(), s);
-        p_begin.upload(begin.data(), begin.size(), s);
-        p_end.upload(end.data(), end.size(), s);
-        p_slot.upload(slot.data(), slot.size(), s);
-        if (n_long) {
-            l_row.upload(lrow.data(), lrow.size(), s);
-            l_first.upload(lfirst.data(), lfirst.size(), s);
-            l_count.upload(lcount.data(), lcount.size(), s);
-        }
-        MI_HIP(hipStreamSynchronize(s));              // the vectors above go out of scope
-        return 4 * (nnz * (ones ? 1 : 2) + 4 * row.size() + 3 * lrow.size());
     }
-};
+    n_pieces = (int)row.size();
+    n_long = (int)lrow.size();
+    const size_t nnz = (size_t)row_ptr[n];
+    idx.alloc(std::max<size_t>(nnz, 1));
+    if (nnz) MI_HIP(hipMemcpyAsync(idx.ptr, row_idx, nnz * sizeof(int), hipMemcpyHostToDevice, s));
+    if (!ones) {
+        val.alloc(std::max<size_t>(nnz, 1));
+        if (nnz) MI_HIP(hipMemcpyAsync(val.ptr, row_val, nnz * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    p_row.upload(row.data(), row.size(), s);
+    p_begin.upload(begin.data(), begin.size(), s);
+    p_end.upload(end.data(), end.size(), s);
+    p_slot.upload(slot.data(), slot.size(), s);
+    if (n_long) {
+        l_row.upload(lrow.data(), lrow.size(), s);
+        l_first.upload(lfirst.data(), lfirst.size(), s);
+        l_count.upload(lcount.data(), lcount.size(), s);
+    }
+    MI_HIP(hipStreamSynchronize(s));              // the vectors above go out of scope
+    return 4 * (nnz * (ones ? 1 : 2) + 4 * row.size() + 3 * lrow.size());
+}
 
-}  // namespace
+int spmm_enqueue(const Side &sd, const float *val, const float *X, int r, float *Y, float *partial, hipStream_t s) {
+    const int lp_shift = r <= 16 ? 4 : (r <= 32 ? 5 : 6);
+    const int grid = div_up((int64_t)sd.n_pieces << lp_shift, SPMM_THREADS);
+    if (!val)
+        hipLaunchKernelGGL(svd_spmm_kernel<true>, dim3(grid), dim3(SPMM_THREADS), 0, s, sd.p_row.ptr, sd.p_begin.ptr, sd.p_end.ptr,
+                           sd.p_slot.ptr, sd.n_pieces, sd.idx.ptr, (const float *)nullptr, X, r, lp_shift, Y, partial);
+    else
+        hipLaunchKernelGGL(svd_spmm_kernel<false>, dim3(grid), dim3(SPMM_THREADS), 0, s, sd.p_row.ptr, sd.p_begin.ptr, sd.p_end.ptr,
+                           sd.p_slot.ptr, sd.n_pieces, sd.idx.ptr, val, X, r, lp_shift, Y, partial);
+    MI_HIP(hipGetLastError());
+    if (sd.n_long) {
+        hipLaunchKernelGGL(svd_long_rows_kernel, dim3(sd.n_long), dim3(256), 0, s, sd.l_row.ptr, sd.l_first.ptr, sd.l_count.ptr, partial, r, Y);
+        MI_HIP(hipGetLastError());
+    }
+    return sd.n_long ? 2 : 1;
+}
+
+size_t GramPlan::make(int n, int r) {
+    const int nt = div_up(r, GT), pairs = nt * (nt + 1) / 2;
+    slabs = std::max(1, std::min(div_up(n, 4 * GR), 1024 / pairs));
+    rows = div_up(div_up(n, slabs), GR) * GR;
+    slabs = div_up(n, rows);
+    return (size_t)slabs * r * r;
+}
+
+void gram_enqueue(const float *X, int n, int r, const GramPlan &plan, double *part, double *G, hipStream_t s) {
+    const int nt = div_up(r, GT);
+    hipLaunchKernelGGL(svd_gram_kernel, dim3(nt, nt, plan.slabs), dim3(256), 0, s, X, n, r, plan.rows, part);
+    MI_HIP(hipGetLastError());
+    hipLaunchKernelGGL(svd_gram_reduce_kernel, dim3(div_up((int64_t)r * r, 256)), dim3(256), 0, s, part, plan.slabs, r, G);
+    MI_HIP(hipGetLastError());
+}
+
+void iota_enqueue(int *out, int n, hipStream_t s) {
+    hipLaunchKernelGGL(svd_iota_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, out, n);
+    MI_HIP(hipGetLastError());
+}
+
+}  // namespace mi355rec
 
 struct mi355rec_svd : Handle {
     int n_users = 0, n_items = 0, r = 0, ones = 0;
@@ -228,7 +266,7 @@ struct mi355rec_svd : Handle {
     DeviceBuffer<float> block[2], tmp, partial, T;
     DeviceBuffer<double> gram_part, G;
     DeviceBuffer<int> iota;
-    int gram_slabs[2] = {0, 0}, gram_rows[2] = {0, 0};
+    GramPlan gram_plan[2];
     double phase_ms[3] = {0, 0, 0};                   // products, Gram, apply
     int64_t launches = 0, calls = 0, create_bytes = 0, h2d_bytes = 0, d2h_bytes = 0;
 
@@ -268,22 +306,14 @@ extern "C" int mi355rec_svd_create(mi355rec_svd_t *out, int32_t n_users, int32_t
         h->block[1].alloc_zero(cap, s);
         h->tmp.alloc(cap);
         h->partial.alloc((size_t)std::max(1, std::max(h->sides[0].n_slots, h->sides[1].n_slots)) * r);
-        const int nt = div_up(r, GT), pairs = nt * (nt + 1) / 2;
         size_t part_cells = 1;
-        for (int sd = 0; sd < 2; ++sd) {
-            const int n = h->rows_of(sd);
-            const int slabs = std::max(1, std::min(div_up(n, 4 * GR), 1024 / pairs));
-            h->gram_rows[sd] = div_up(div_up(n, slabs), GR) * GR;
-            h->gram_slabs[sd] = div_up(n, h->gram_rows[sd]);
-            part_cells = std::max(part_cells, (size_t)h->gram_slabs[sd] * r * r);
-        }
+        for (int sd = 0; sd < 2; ++sd) part_cells = std::max(part_cells, h->gram_plan[sd].make(h->rows_of(sd), r));
         h->gram_part.alloc(part_cells);
         h->G.alloc((size_t)r * r);
         h->T.alloc((size_t)r * r);
         const int n_max = std::max(n_users, n_items);
         h->iota.alloc(n_max);
-        hipLaunchKernelGGL(svd_iota_kernel, dim3(div_up(n_max, 256)), dim3(256), 0, s, h->iota.ptr, n_max);
-        MI_HIP(hipGetLastError());
+        iota_enqueue(h->iota.ptr, n_max, s);
         MI_HIP(hipStreamSynchronize(s));
         *out = h.release();
     });
@@ -323,28 +353,15 @@ extern "C" int mi355rec_svd_product(mi355rec_svd_t h, int32_t dst_side) {
         hipStream_t s = h->stream;
         const Side &sd = h->sides[dst_side];
         const int r = h->r;
-        const int lp_shift = r <= 16 ? 4 : (r <= 32 ? 5 : 6);
         const float *X = h->block[1 - dst_side].ptr;
         float *Y = h->block[dst_side].ptr;
-        const int grid = div_up((int64_t)sd.n_pieces << lp_shift, SPMM_THREADS);
         h->timer.start(s);
-        if (h->ones)
-            hipLaunchKernelGGL(svd_spmm_kernel<true>, dim3(grid), dim3(SPMM_THREADS), 0, s, sd.p_row.ptr, sd.p_begin.ptr, sd.p_end.ptr,
-                               sd.p_slot.ptr, sd.n_pieces, sd.idx.ptr, (const float *)nullptr, X, r, lp_shift, Y, h->partial.ptr);
-        else
-            hipLaunchKernelGGL(svd_spmm_kernel<false>, dim3(grid), dim3(SPMM_THREADS), 0, s, sd.p_row.ptr, sd.p_begin.ptr, sd.p_end.ptr,
-                               sd.p_slot.ptr, sd.n_pieces, sd.idx.ptr, sd.val.ptr, X, r, lp_shift, Y, h->partial.ptr);
-        MI_HIP(hipGetLastError());
-        if (sd.n_long) {
-            hipLaunchKernelGGL(svd_long_rows_kernel, dim3(sd.n_long), dim3(256), 0, s, sd.l_row.ptr, sd.l_first.ptr, sd.l_count.ptr,
-                               h->partial.ptr, r, Y);
-            MI_HIP(hipGetLastError());
-        }
+        const int launched = spmm_enqueue(sd, h->ones ? nullptr : sd.val.ptr, X, r, Y, h->partial.ptr, s);
         h->timer.stop(s);
         MI_HIP(hipStreamSynchronize(s));
         const double ms = h->timer.elapsed_ms();
         h->phase_ms[0] += ms;
-        h->launches += sd.n_long ? 2 : 1;
+        h->launches += launched;
         ++h->calls;
         h->stats = mi355rec_stats{};
         h->stats.call_ms = h->stats.kernel_ms = ms;
@@ -361,14 +378,9 @@ extern "C" int mi355rec_svd_gram(mi355rec_svd_t h, int32_t side, double *G) {
         MI_REQUIRE(side == 0 || side == 1, "side %d: 0 (users x r) or 1 (items x r)", side);
         ensure_device();
         hipStream_t s = h->stream;
-        const int r = h->r, n = h->rows_of(side), nt = div_up(r, GT);
+        const int r = h->r, n = h->rows_of(side);
         h->timer.start(s);
-        hipLaunchKernelGGL(svd_gram_kernel, dim3(nt, nt, h->gram_slabs[side]), dim3(256), 0, s, h->block[side].ptr, n, r, h->gram_rows[side],
-                           h->gram_part.ptr);
-        MI_HIP(hipGetLastError());
-        hipLaunchKernelGGL(svd_gram_reduce_kernel, dim3(div_up((int64_t)r * r, 256)), dim3(256), 0, s, h->gram_part.ptr, h->gram_slabs[side], r,
-                           h->G.ptr);
-        MI_HIP(hipGetLastError());
+        gram_enqueue(h->block[side].ptr, n, r, h->gram_plan[side], h->gram_part.ptr, h->G.ptr, s);
         h->timer.stop(s);
         h->G.download(G, (size_t)r * r, s);
         MI_HIP(hipStreamSynchronize(s));

@@ -23,6 +23,7 @@ from .graph_based import _P3alphaLogic, _RP3betaLogic
 from .ials import _IALSLogic
 from .knn import _ItemKNNLogic, _UserKNNLogic
 from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
+from .nmf import _NMFLogic
 from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
 from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin
 from .slim_bpr import _SLIMLogic
@@ -44,6 +45,7 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         "SLIMElasticNetRecommender": (_SLIMElasticNetLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "PureSVDRecommender": (_PureSVDLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
         "PureSVDItemRecommender": (_PureSVDItemLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
+        "NMFRecommender": (_NMFLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
         "ItemKNNCFRecommender": (_ItemKNNLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "UserKNNCFRecommender": (_UserKNNLogic,) + sim_score + (BaseUserSimilarityMatrixRecommender,),
         "P3alphaRecommender": (_P3alphaLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
