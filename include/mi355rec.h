@@ -511,6 +511,18 @@ int mi355rec_scorer_update(mi355rec_scorer_t h, const float *U, const float *V, 
  * order, -1 padded where fewer finite scores exist.  scores (nullable, n x n_items) receives the filtered score matrix. */
 int mi355rec_scorer_recommend(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
                               const uint8_t *item_allowed, int32_t *ranked, float *scores);
+/* Candidate rows (the reference's EvaluatorNegativeItemSample, Base/Evaluation/Evaluator.py:455-539, hands each user's test items and
+ * sampled negatives to recommend() as items_to_compute, Base/BaseRecommender.py:131-222): row r of the CSR (cand_indptr[n + 1],
+ * cand_indices; item ids strictly ascending inside a row, else MI355REC_E_INVALID) holds the only items user_ids[r] may be given.
+ * U[u] . V[c] (+ biases) is computed for those items alone -- no score matrix -- then the mask / seen filters of
+ * mi355rec_scorer_recommend; ranked[(row) * cutoff ...] = the cutoff best candidates, descending, ties towards the lower item id,
+ * -1 padded.  Rows of more than 4096 items and cutoffs above 4096 are MI355REC_E_UNSUPPORTED.  get_stats afterwards: kernel_ms =
+ * call_ms = the candidate kernel(s) (there is no GEMM to tell apart), n_units = n; no flop or byte figures. */
+int mi355rec_scorer_recommend_candidates(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
+                                         const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen, const uint8_t *item_allowed,
+                                         int32_t *ranked);
+/* Cells of the handle's n x n_items score buffer (0 until a full-row call has needed it): candidate calls leave it alone. */
+int mi355rec_scorer_score_capacity(mi355rec_scorer_t h, int64_t *cells);
 int mi355rec_scorer_get_stats(mi355rec_scorer_t h, mi355rec_stats *stats);
 void mi355rec_scorer_destroy(mi355rec_scorer_t h);
 
@@ -524,6 +536,11 @@ int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_users, int32_t 
                              const int32_t *seen_indptr, const int32_t *seen_indices);
 int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
                                 const uint8_t *item_allowed, int32_t *ranked, float *scores);
+/* As mi355rec_scorer_recommend_candidates; the score row is accumulated as in mi355rec_spscorer_recommend and only the candidates
+ * are read from it. */
+int mi355rec_spscorer_recommend_candidates(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
+                                           const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
+                                           const uint8_t *item_allowed, int32_t *ranked);
 int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 
@@ -560,6 +577,16 @@ int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_
                              const uint8_t *item_allowed);
 int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                const uint8_t *item_allowed);
+/* Negative-sample evaluation (Evaluator.py:455-539 EvaluatorNegativeItemSample): the candidate rows of ALL n_users users as CSR
+ * (indptr[n_users + 1]; item ids strictly ascending inside a row, else MI355REC_E_INVALID), uploaded once per evaluator.
+ * MI355REC_E_UNSUPPORTED when a row holds more than 4096 items or the lists are more than 4096 wide. */
+int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *indptr, const int32_t *indices);
+/* mi355rec_eval_add_scorer / mi355rec_eval_add_spscorer with every user ranking the candidates of its row only (as
+ * mi355rec_*scorer_recommend_candidates).  The two functions above are not affected by mi355rec_eval_set_candidates. */
+int mi355rec_eval_add_scorer_candidates(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                        const uint8_t *item_allowed);
+int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                          const uint8_t *item_allowed);
 /* sums[c * MI355REC_EVAL_VALUES + v]: value v summed over the evaluated users in a fixed order (the last one is the covered-user
  * count); item_counts[c * n_items + i]: times item i was recommended within cutoff c (the recommended_counter of
  * metrics.py:284-286, 762-769). */

@@ -168,10 +168,13 @@ SIGNATURES = {
     "mi355rec_scorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),
     "mi355rec_scorer_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32]),
     "mi355rec_scorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_scorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "mi355rec_scorer_score_capacity": (C.c_int, [_vp, C.POINTER(_i64)]),
     "mi355rec_scorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_scorer_destroy": (None, [_vp]),
     "mi355rec_spscorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32] + [_vp] * 8),
     "mi355rec_spscorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_spscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mi355rec_spscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_spscorer_destroy": (None, [_vp]),
     "mi355rec_eval_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
@@ -179,6 +182,9 @@ SIGNATURES = {
     "mi355rec_eval_add_lists": (C.c_int, [_vp, _i32, _i32, _vp]),
     "mi355rec_eval_add_scorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_spscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_set_candidates": (C.c_int, [_vp, _vp, _vp]),
+    "mi355rec_eval_add_scorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_spscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_finish": (C.c_int, [_vp, _vp, _vp]),
     "mi355rec_eval_get_per_user": (C.c_int, [_vp, _vp]),
     "mi355rec_eval_destroy": (None, [_vp]),

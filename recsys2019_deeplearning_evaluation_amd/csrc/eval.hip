@@ -10,7 +10,9 @@
 //   eval_sum_kernel     each (cutoff, value) column summed over all users in a fixed order (no floating-point atomics).
 //   eval_counts_kernel  counts[b] -> counts of every cutoff: a running sum over b.
 // The lists come either from a device scorer (score.hip: scorer_enqueue / spscorer_enqueue, the kernel runs on the scorer's
-// stream and reads its `ranked` buffer in place) or from the host (the lists path).
+// stream and reads its `ranked` buffer in place) or from the host (the lists path).  For the reference's EvaluatorNegativeItemSample
+// (Evaluator.py:455-539) the scorers rank each user's candidate row only (cand.hip: *_enqueue_candidates; the rows are uploaded once
+// by mi355rec_eval_set_candidates); the metric kernel and finish are the same.
 #include "common.h"
 #include "score.h"
 #include "wave.cuh"
@@ -227,6 +229,8 @@ struct mi355rec_eval : Handle {
     DeviceBuffer<float> test_rel, idcg, logs;
     DeviceBuffer<double> novelty, popularity, vals, sums;
     DeviceBuffer<unsigned char> allowed;
+    DeviceBuffer<int> cand_ptr, cand_idx;       // candidate rows of every user (mi355rec_eval_set_candidates)
+    int cand_longest = -1;                      // -1: no candidate rows
 
     ~mi355rec_eval() {
         shutdown([&] {
@@ -401,6 +405,48 @@ extern "C" int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t sco
 extern "C" int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                           const uint8_t *item_allowed) {
     return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue); });
+}
+
+// Negative-sample evaluation (Evaluator.py:455-539, EvaluatorNegativeItemSample): every user ranks the candidates of its row only.
+extern "C" int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *indptr, const int32_t *indices) {
+    return guarded([&] {
+        MI_REQUIRE(h && indptr, "NULL argument");
+        check_candidate_cutoff(h->width);
+        const int longest = check_candidate_rows(indptr, indices, h->n_users, h->n_items);
+        ensure_device();
+        hipStream_t s = h->stream;
+        MI_HIP(hipEventSynchronize(h->done));           // (a block still running may read the old rows)
+        h->cand_longest = -1;
+        const size_t nnz = (size_t)indptr[h->n_users];
+        h->cand_ptr.upload(indptr, (size_t)h->n_users + 1, s);
+        if (nnz) h->cand_idx.upload(indices, nnz, s);
+        else h->cand_idx.alloc(1);
+        MI_HIP(hipStreamSynchronize(s));
+        h->cand_longest = longest;
+    });
+}
+
+namespace {
+template <class Scorer, class Enqueue>
+void add_from_scorer_candidates(mi355rec_eval *h, Scorer *sc, int first, int n, int remove_seen, const uint8_t *allowed, Enqueue enqueue) {
+    MI_REQUIRE(h, "NULL argument");
+    MI_REQUIRE(h->cand_longest >= 0, "mi355rec_eval_set_candidates has not been called");
+    const CandidateRows rows{h->cand_ptr.ptr, h->cand_idx.ptr, true, h->cand_longest};
+    add_from_scorer(h, sc, first, n, remove_seen, allowed,
+                    [&](Scorer *scorer, const int *users, int count, int cutoff, int seen, const unsigned char *mask, bool) {
+                        return enqueue(scorer, users, count, cutoff, seen, mask, rows);
+                    });
+}
+}  // namespace
+
+extern "C" int mi355rec_eval_add_scorer_candidates(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n,
+                                                   int32_t remove_seen, const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, scorer_enqueue_candidates); });
+}
+
+extern "C" int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n,
+                                                     int32_t remove_seen, const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue_candidates); });
 }
 
 extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts) {

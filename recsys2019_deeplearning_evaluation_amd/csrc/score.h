@@ -1,6 +1,7 @@
 // score.h -- the two scorer handles and the "score + rank on the handle's stream" half of mi355rec_scorer_recommend /
 // mi355rec_spscorer_recommend (score.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists
-// where these leave them.
+// where these leave them; and the same for candidate rows (cand.hip: mi355rec_*scorer_recommend_candidates, the negative-sample
+// evaluator).
 #pragma once
 
 #include "common.h"
@@ -25,6 +26,7 @@ struct ScorerHandle : Handle {
     WideRanker wide;
     int n_users = 0, n_items = 0;       // rows that can be asked for, width of a score row
     DeviceBuffer<int> seen_ptr, seen_idx, users, ranked;
+    DeviceBuffer<int> cand_ptr, cand_idx;   // the candidate rows of the last mi355rec_*scorer_recommend_candidates
     DeviceBuffer<float> scores;
     DeviceBuffer<unsigned char> allowed;
 };
@@ -61,6 +63,34 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
                        bool keep_scores);
 Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                          bool keep_scores);
+// ---- candidate rows: each user ranks a short list of items of its own (Evaluator.py:455-539, EvaluatorNegativeItemSample) ----------
+constexpr int CAND_MAX = 4096;          // longest candidate row: one block_rank_emit (topk.cuh) over the whole row
+
+// a CSR of candidate rows on the device, item ids strictly ascending inside a row (check_candidate_rows)
+struct CandidateRows {
+    const int *ptr, *idx;
+    bool by_user;           // the row of batch entry b is users[b] (one row per user of the model), not b
+    int longest;            // entries of the longest row (sizes the LDS candidate buffer)
+};
+
+// Host check of a candidate CSR: monotone indptr starting at 0, ids inside [0, n_items) and strictly ascending in every row
+// (MI355REC_E_INVALID), no row longer than CAND_MAX (MI355REC_E_UNSUPPORTED).  Returns the length of the longest row.
+int check_candidate_rows(const int32_t *indptr, const int32_t *indices, int n_rows, int n_items);
+void check_candidate_cutoff(int cutoff);    // a list wider than MAX_TOPK (topk.cuh) is MI355REC_E_UNSUPPORTED: the one place that says so
+
+// scorer_enqueue / spscorer_enqueue over candidate rows: only a user's candidates are ranked (value descending, ties towards the
+// lower item id), after the same seen / mask filters.  The factor scorer computes U[u] . V[c] for the candidates alone -- no GEMM, no
+// score matrix; the sparse scorer accumulates its row as before and gathers the candidates from it.  `timer` spans the candidate
+// kernel(s) (mi355rec_*scorer_recommend_candidates reports it as kernel_ms and call_ms); `call_timer` is not used.
+Ranking scorer_enqueue_candidates(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                  const CandidateRows &rows);
+Ranking spscorer_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
+                                    const unsigned char *allowed, const CandidateRows &rows);
+// what cand.hip takes from score.hip (host functions): whether a score row of n_items floats is ranked in LDS at this cutoff, and
+// spscorer_enqueue's accumulation of rows that are not -- h->scores[b][n_items] = A[users[b], :] . B, zeroed first, unfiltered, not
+// ranked; the caller has grown h->scores.
+bool score_row_fits_lds(int n_items, int cutoff);
+void spscorer_enqueue_wide_rows(mi355rec_spscorer_t h, const int *users, int n);
 // C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's
 // f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
 void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);

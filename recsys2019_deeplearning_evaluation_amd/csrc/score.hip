@@ -612,3 +612,24 @@ extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t 
 extern "C" int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
 extern "C" void mi355rec_spscorer_destroy(mi355rec_spscorer_t h) { handle_destroy(h); }
+
+// ---- what the candidate-row kernels (cand.hip) need of this file: host code only ----------------------------------------
+namespace mi355rec {
+
+bool score_row_fits_lds(int n_items, int cutoff) { return fits_lds_rank(n_items, cutoff); }
+
+// spscorer_enqueue's accumulation for rows in HBM, without the ranking: h->scores[b][n_items] = A[users[b], :] . B, unfiltered.
+// The caller has grown h->scores (after the stream had drained).
+void spscorer_enqueue_wide_rows(mi355rec_spscorer_t h, const int *users, int n) {
+    hipStream_t s = h->stream;
+    SpScoreParams p{};
+    p.n_out = h->n_items; p.n_pad = (h->n_items + 3) & ~3;
+    p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
+    p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
+    p.users = users; p.scores = h->scores.ptr;
+    MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_items, s));
+    hipLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, p);
+    MI_HIP(hipGetLastError());
+}
+
+}  // namespace mi355rec

@@ -7,6 +7,8 @@ their `evaluator_object` unchanged.  Two paths:
   fused  recommenders with a device scorer (GpuScoringMixin / GpuSimilarityScoringMixin): each block of users is scored,
          ranked and evaluated on the device; neither scores nor lists reach the host.
   lists  any other recommender: recommend(..., return_scores=False) on the host, the lists uploaded, the same metric kernel.
+`EvaluatorNegativeItemSample_MI355X` is the reference's EvaluatorNegativeItemSample (Evaluator.py:455-539) on the same two paths: every
+user ranks its own candidates only (its test items plus the sampled negatives), the metrics are the parent's.
 Given the same lists, both give bitwise the same result, whatever the block size.  (The sparse scorer sums with LDS float atomics, so
 its order of near-tied scores, and with it a list, can change from one call to the next.)  O(n_items) population metrics (coverage, Gini, Shannon,
 Herfindahl, mean inter-list diversity) and F1 are finished here in float64 from the device's item counters.
@@ -98,6 +100,21 @@ def item_terms(URM_train):
     return novelty, popularity_norm
 
 
+def users_to_evaluate(URM_test, min_ratings_per_user=1, ignore_items=None, ignore_users=None):
+    """The evaluated users, ascending (int32; the reference iterates a set: order undefined there), and the mask of the users with
+    enough test ratings: the copy of URM_test pruned of ignore_items decides who has `min_ratings_per_user` of them
+    (Evaluator.py:124-138, 180-202), ignore_users are taken out afterwards (:204-211)."""
+    pruned = sps.csr_matrix(URM_test).tocsc(copy=True)
+    for item in np.asarray([] if ignore_items is None else ignore_items).astype(np.int64):
+        pruned.data[pruned.indptr[item]:pruned.indptr[item + 1]] = 0
+    pruned.eliminate_zeros()
+    mask = np.ediff1d(sps.csr_matrix(pruned).indptr) >= min_ratings_per_user
+    users = np.arange(pruned.shape[0])[mask]
+    if ignore_users is not None:
+        users = np.setdiff1d(users, np.array(ignore_users))
+    return np.sort(users).astype(np.int32), mask
+
+
 class EvaluatorHoldout_MI355X(N.Handle):
     """EvaluatorHoldout (Evaluator.py:382) on the device.  See the module docstring."""
     _PREFIX = "mi355rec_eval"
@@ -125,23 +142,13 @@ class EvaluatorHoldout_MI355X(N.Handle):
         self.n_users, self.n_items = self.URM_test.shape
         self.width = min(self.max_cutoff, self.n_items)
 
-        # users: the copy pruned of ignore_items decides who has enough test ratings (Evaluator.py:124-138, 180-202), minus ignore_users (:204-211)
-        pruned = self.URM_test.tocsc(copy=True)
-        for item in self.ignore_items_ID.astype(np.int64):
-            pruned.data[pruned.indptr[item]:pruned.indptr[item + 1]] = 0
-        pruned.eliminate_zeros()
-        mask = np.ediff1d(sps.csr_matrix(pruned).indptr) >= min_ratings_per_user
+        self.users_to_evaluate, mask = users_to_evaluate(self.URM_test, min_ratings_per_user, self.ignore_items_ID, ignore_users)
         if not np.all(mask):
             self._print("Ignoring {} ({:.2f}%) Users that have less than {} test interactions".format(
                 np.sum(mask), 100 * np.sum(np.logical_not(mask)) / len(mask), min_ratings_per_user))
-        users = np.arange(self.n_users)[mask]
         if ignore_users is not None:
             self._print("Ignoring {} Users".format(len(ignore_users)))
-            self.ignore_users_ID = np.array(ignore_users)
-            users = np.setdiff1d(users, self.ignore_users_ID)
-        else:
-            self.ignore_users_ID = np.array([])
-        self.users_to_evaluate = np.sort(users).astype(np.int32)       # (the reference iterates a set: order undefined there)
+        self.ignore_users_ID = np.array([]) if ignore_users is None else np.array(ignore_users)
 
         # relevant items and ratings: URM_test as passed (Evaluator.py:171, 279-291)
         indptr, indices = N.as_i32(self.URM_test.indptr), N.as_i32(self.URM_test.indices)
@@ -182,13 +189,7 @@ class EvaluatorHoldout_MI355X(N.Handle):
                 results = {c: {m: 0.0 for m in METRICS} for c in self.cutoff_list}
                 return results, get_result_string(results)
             self._call("begin", N.ptr(novelty), N.ptr(popularity_norm), N.ptr(users), n_eval)
-            block = int(block_size) if block_size else self._block_size()
-            if isinstance(rec, GpuScoringMixin):
-                self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
-            elif isinstance(rec, GpuSimilarityScoringMixin):
-                self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
-            else:
-                self._run_lists(rec, block)
+            self._run(rec, block_size)
             sums = np.zeros((len(self.cutoff_list), N_VALUES), np.float64)
             counts = np.zeros((len(self.cutoff_list), self.n_items), np.int32)
             self._call("finish", N.ptr(sums), N.ptr(counts))
@@ -210,6 +211,16 @@ class EvaluatorHoldout_MI355X(N.Handle):
             n_eval, 100.0, elapsed, n_eval / max(elapsed, 1e-9)))
         sys.stdout.flush()
         return results, get_result_string(results)
+
+    def _run(self, rec, block_size):
+        """Every block of users through the fused path of the recommender's device scorer, or through its recommend()."""
+        block = int(block_size) if block_size else self._block_size()
+        if isinstance(rec, GpuScoringMixin):
+            self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
+        elif isinstance(rec, GpuSimilarityScoringMixin):
+            self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
+        else:
+            self._run_lists(rec, block)
 
     def _run_fused(self, scorer, add, rec, block):
         allowed = allowed_items(rec, remove_custom_items_flag=self.ignore_items_flag)
@@ -248,3 +259,85 @@ class EvaluatorHoldout_MI355X(N.Handle):
                 self._per_user = out
         return {cutoff: {m: self._per_user[:, c, v].copy() for v, m in enumerate(PER_USER)}
                 for c, cutoff in enumerate(self.cutoff_list)}
+
+
+def items_to_rank(URM_test, URM_test_negative):
+    """URM_items_to_rank of EvaluatorNegativeItemSample (Evaluator.py:484-486): per user, the columns with a non-zero stored value
+    in URM_test or in URM_test_negative, each once, as a CSR of ones with the rows sorted by item id."""
+    test, negative = sps.csr_matrix(URM_test), sps.csr_matrix(URM_test_negative)
+    if test.shape != negative.shape:
+        raise ValueError("URM_test is {}, URM_test_negative {}".format(test.shape, negative.shape))
+    rows, cols = [], []
+    for m in (test, negative):
+        keep = m.data != 0
+        rows.append(np.repeat(np.arange(m.shape[0]), np.ediff1d(m.indptr))[keep])
+        cols.append(m.indices[keep])
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    union = sps.csr_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=test.shape)
+    union.sum_duplicates()
+    union.sort_indices()
+    union.data = np.ones(len(union.data), np.float64)
+    return union
+
+
+class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
+    """EvaluatorNegativeItemSample (Evaluator.py:455-539) on the device: the candidates of a user are its test items and the items
+    of its row of URM_test_negative; its list is the `max_cutoff` best of them after the seen / ignored-item filters
+    (BaseRecommender.py:131-222 with items_to_compute), ties towards the lower item id.  Users, relevance and every metric are the
+    parent's.  Recommenders with a device scorer score and rank the candidates on the device (no score matrix); any other
+    recommender is asked once per user, as the reference asks.  Candidate rows of more than 4096 items, or lists wider than that,
+    send every recommender through recommend()."""
+
+    EVALUATOR_NAME = "EvaluatorNegativeItemSample_MI355X"
+    FUSED_BLOCK = 16384             # users per launch of the factor scorer's candidate kernel (there is no n x n_items buffer to bound)
+
+    def __init__(self, URM_test_list, URM_test_negative, cutoff_list, min_ratings_per_user=1, exclude_seen=True, diversity_object=None,
+                 ignore_items=None, ignore_users=None, verbose=True):
+        if isinstance(URM_test_list, list):
+            raise ValueError("List of URM_test not supported")
+        if tuple(URM_test_list.shape) != tuple(URM_test_negative.shape):
+            raise ValueError("URM_test is {}, URM_test_negative {}".format(URM_test_list.shape, URM_test_negative.shape))
+        super().__init__(URM_test_list, cutoff_list, min_ratings_per_user=min_ratings_per_user, exclude_seen=exclude_seen,
+                         diversity_object=diversity_object, ignore_items=ignore_items, ignore_users=ignore_users, verbose=verbose)
+        self.URM_items_to_rank = items_to_rank(self.URM_test, URM_test_negative)       # (URM_test as passed: not pruned of ignore_items)
+        indptr, indices = N.as_i32(self.URM_items_to_rank.indptr), N.as_i32(self.URM_items_to_rank.indices)
+        try:
+            self._call("set_candidates", N.ptr(indptr), N.ptr(indices))
+            self.candidates_on_device = True
+        except NotImplementedError as unsupported:
+            self.candidates_on_device = False
+            self._print("every recommender goes through recommend(), one user at a time: {}".format(unsupported))
+
+    def _candidates(self, user):
+        rows = self.URM_items_to_rank
+        return rows.indices[rows.indptr[user]:rows.indptr[user + 1]]
+
+    def _run(self, rec, block_size):
+        n_eval = len(self.users_to_evaluate)
+        if self.candidates_on_device and isinstance(rec, GpuScoringMixin):
+            self._run_fused(rec._get_scorer(), "add_scorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
+        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin):
+            self._run_fused(rec._get_sparse_scorer(), "add_spscorer_candidates", rec, int(block_size) if block_size else self._block_size())
+        else:
+            self._run_lists(rec, int(block_size) if block_size else self._block_size())
+
+    def _run_lists(self, rec, block):
+        """Evaluator.py:519-530: recommend() per user with the user's candidates as items_to_compute; the lists of a block of users go
+        up together."""
+        users = self.users_to_evaluate
+        for start in range(0, len(users), block):
+            batch = users[start:start + block]
+            table = np.full((len(batch), self.width), -1, np.int32)
+            for r, user in enumerate(batch):
+                lists = rec.recommend(np.atleast_1d(user), remove_seen_flag=self.exclude_seen, cutoff=self.max_cutoff,
+                                      remove_top_pop_flag=False, items_to_compute=self._candidates(user),
+                                      remove_custom_items_flag=self.ignore_items_flag, return_scores=False)
+                if len(lists) != 1:
+                    raise ValueError("{}: recommend() returned {} lists for one user".format(self.EVALUATOR_NAME, len(lists)))
+                items = np.asarray(lists[0]).ravel()
+                if len(items) > self.width:
+                    raise ValueError("{}: a list of {} items for cutoff {}".format(self.EVALUATOR_NAME, len(items), self.max_cutoff))
+                if len(items) and (items.min() < 0 or items.max() >= self.n_items):
+                    raise ValueError("{}: recommended item id outside [0, {})".format(self.EVALUATOR_NAME, self.n_items))
+                table[r, :len(items)] = items
+            self._call("add_lists", start, len(batch), N.ptr(table))

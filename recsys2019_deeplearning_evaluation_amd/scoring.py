@@ -7,7 +7,10 @@ reference's evaluation loop asks on every validation (Base/Evaluation/Evaluator.
 `GpuScoringMixin` plugs it under `recommend()` of a BaseMatrixFactorizationRecommender without changing its signature;
 `_compute_item_score` itself is left untouched (host NumPy), so either path can be checked against the other.
 """
+import ctypes as C
+
 import numpy as np
+import scipy.sparse as sps
 
 from . import _native as N
 
@@ -24,6 +27,25 @@ class _Scorer(N.Handle):
         mask = None if allowed_items is None else np.ascontiguousarray(allowed_items, dtype=np.uint8)
         self._call("recommend", N.ptr(users), len(users), cutoff, int(bool(remove_seen)), N.ptr(mask), N.ptr(ranked), N.ptr(scores))
         return ranked, scores
+
+    def recommend_candidates(self, user_id_array, candidates_csr, cutoff, remove_seen=True, allowed_items=None):
+        """Row r of `candidates_csr` (n x n_items; stored zeros dropped) holds the only items user_id_array[r] may be given: what
+        recommend(..., items_to_compute=row) ranks (BaseRecommender.py:131-222), for a batch of users with a row each
+        (EvaluatorNegativeItemSample, Evaluator.py:455-539).  int32 (n, cutoff), -1 padded; ties go to the lower item id."""
+        users = N.as_i32(np.atleast_1d(user_id_array))
+        rows = sps.csr_matrix(candidates_csr, copy=True)
+        if rows.shape != (len(users), self.n_items):
+            raise ValueError("candidates_csr is {}, expected {}".format(rows.shape, (len(users), self.n_items)))
+        rows.eliminate_zeros()
+        rows.sum_duplicates()
+        rows.sort_indices()
+        cutoff = int(min(cutoff, self.n_items))
+        ranked = np.empty((len(users), cutoff), np.int32)
+        mask = None if allowed_items is None else np.ascontiguousarray(allowed_items, dtype=np.uint8)
+        indptr, indices = N.as_i32(rows.indptr), N.as_i32(rows.indices)
+        self._call("recommend_candidates", N.ptr(users), len(users), N.ptr(indptr), N.ptr(indices), cutoff, int(bool(remove_seen)),
+                   N.ptr(mask), N.ptr(ranked))
+        return ranked
 
 
 class MI355XScorer(_Scorer):
@@ -48,6 +70,13 @@ class MI355XScorer(_Scorer):
         bu = N.as_f32(USER_bias) if self.use_bias else None
         bi = N.as_f32(ITEM_bias) if self.use_bias else None
         self._call("update", N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), float(np.asarray(GLOBAL_bias)))
+
+    def score_capacity(self):
+        """Cells of the device buffer for (users x n_items) score rows: 0 until a full-row recommend() has needed it; the candidate
+        path never touches it."""
+        cells = C.c_int64(0)
+        self._call("score_capacity", C.byref(cells))
+        return int(cells.value)
 
 
 def _fingerprint(array):
