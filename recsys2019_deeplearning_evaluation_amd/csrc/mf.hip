@@ -164,13 +164,17 @@ void fill_params(mi355rec_mf *h, MfParams<T> &p) {
 // 140 M samples/s instead of 176 M, the 32-model group 567 M instead of 678 M.)
 template <int ALGO, class T, int VEC, int LPR, int KI>
 void launch_batch_as(mi355rec_mf *h, const MfParams<T> &p, int grid, int batch_local, hipEvent_t e0, hipEvent_t e1) {
-    if (p.sgd_mode == MI355REC_SGD) {
-        if (e0) hipExtLaunchKernelGGL((mf_batch_kernel<ALGO, T, VEC, LPR, KI, true>), dim3(grid), dim3(256), 0, h->stream, e0, e1, 0, p, batch_local);
-        else hipLaunchKernelGGL((mf_batch_kernel<ALGO, T, VEC, LPR, KI, true>), dim3(grid), dim3(256), 0, h->stream, p, batch_local);   // capturable
-        return;
-    }
-    if (e0) hipExtLaunchKernelGGL((mf_batch_kernel<ALGO, T, VEC, LPR, KI, false>), dim3(grid), dim3(256), 0, h->stream, e0, e1, 0, p, batch_local);
-    else hipLaunchKernelGGL((mf_batch_kernel<ALGO, T, VEC, LPR, KI, false>), dim3(grid), dim3(256), 0, h->stream, p, batch_local);
+    // what the header's address is made of goes in front of the parameter block (see mf_batch_kernel); constants of the launch, and
+    // of the captured graph node, like batch_local
+    const TaskHeader *hdr = p.tasks + (size_t)batch_local * p.tasks_per_batch;
+    const int4 *slot = p.slot_recs + (size_t)batch_local * p.slot_rec_stride;
+    const int stamps = p.ticks != nullptr;
+    auto go = [&](auto kernel) {
+        if (e0) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, e0, e1, 0, hdr, slot, p.tasks_per_batch, p.wg_base, p.wg_stride, stamps, p, batch_local);
+        else hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, hdr, slot, p.tasks_per_batch, p.wg_base, p.wg_stride, stamps, p, batch_local);   // capturable
+    };
+    if (p.sgd_mode == MI355REC_SGD) go(mf_batch_kernel<ALGO, T, VEC, LPR, KI, true>);
+    else go(mf_batch_kernel<ALGO, T, VEC, LPR, KI, false>);
 }
 
 template <int ALGO, class T>

@@ -98,32 +98,42 @@ __device__ __forceinline__ Rows<T, VEC, KI, BPR> load_rows(const MfParams<T> &p,
 // KI chunks of VEC elements per lane, LPR lanes per row (64 / LPR samples of a task's list in flight per wavefront).
 // `wg` = this workgroup's index within the mini-batch's launch of ONE model (blockIdx.x; the group launch below puts the model
 // on blockIdx.y).
-template <int ALGO, class T, int VEC, int LPR, int KI>
-__device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int batch_local, const int wg) {
+// `hdr` / `slot` = the mini-batch's headers and pair records by slot, `wv` = this wavefront's header slot, `tpb` = header slots per
+// mini-batch, `stamps` = p.ticks != NULL: what the header's address is made of.  The one-model kernel gets them as leading
+// kernel arguments, which gfx950 preloads into scalar registers (ARGS_HERE: the request for the other arguments goes out behind the
+// header's, not in front of it), the group kernel from its table row.
+template <int ALGO, class T, int VEC, int LPR, int KI, bool ARGS_HERE>
+__device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int batch_local, const int wg, const int wv, const int tpb,
+                                              const TaskHeader *hdr, const int4 *slot, const bool stamps) {
     constexpr int G = 64 / LPR;
     constexpr bool BPR = ALGO == MI355REC_MF_BPR;
     using Ch = Chunk<T, VEC>;
     using R = Rows<T, VEC, KI, BPR>;
     const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((wg * p.wg_stride + p.wg_base) * 4 + (threadIdx.x >> 6));
-    const unsigned long long tk0 = p.ticks ? stamp() : 0ull;
+    const unsigned long long tk0 = stamps ? stamp() : 0ull;
     // every wave-uniform input is requested before the first one is waited for (scalar loads, one wait)
     // (unused task slots of a batch are zero: a header with no samples means there is nothing to do)
     // (the grid is rounded up to whole workgroups: wavefronts past the batch's last slot re-read that slot and idle)
+    const TaskHeader *hp = hdr + min(wv, tpb - 1);
+    const int8v hd = *reinterpret_cast<const int8v *>(hp);      // one 32-byte load: header and first record
+    // a pair task's other records: by slot, requested with the header (through the record list they were a dependent round trip
+    // in front of the row gathers of the lane groups 1 .. G - 1: 2 300 cycles until the rows were there against 1 800 for one sample)
+    int4 slot_rec = make_int4(0, 0, 0, 0);
+    if constexpr (BPR && G > 1) slot_rec = slot[(size_t)min(wv, tpb - 1) * 3 + max(lane / LPR - 1, 0)];
+    if constexpr (ARGS_HERE) {
+        // Every other kernel argument the start of the kernel needs is requested in ONE batch of scalar loads, next to the header: left
+        // to itself the compiler fetched them piecewise as the code came to need them -- three waits for a cold kernarg segment
+        // before FunkSVD's row gathers, one for BPR's.
+        asm volatile("" ::"s"(p.ticks), "s"(p.use_bias), "s"(p.sgd_mode), "s"(p.state), "s"(p.mu_state), "s"(p.mu_acc), "s"(p.k), "s"(p.U0),
+                     "s"(p.U1), "s"(p.V0), "s"(p.V1), "s"(p.recs));
+    }
     const bool bias = !BPR && p.use_bias;
     long long gb = batch_local;
-    const TaskHeader *hp = p.tasks + ((size_t)batch_local * p.tasks_per_batch + min(wv, p.tasks_per_batch - 1));
-    const int8v hd = *reinterpret_cast<const int8v *>(hp);      // one 32-byte load: header and first record
     // The global mini-batch index (Adam and the global bias need it) and the global-bias ring entry are requested right behind the
     // header (the wait for the header does not cover younger loads; both were written by the kernel before this one and take
     // 2 400 cycles to arrive where the header, last written by the schedule, takes 900) -- not after it has arrived, and the ring
     // not after the index: a FunkSVD kernel began with three round trips one after the other.  Unconditionally for FunkSVD: a
     // branch around a load makes the compiler wait for it before the next one is issued.
-    // a pair task's other records: by slot, requested with the header (through the record list they were a dependent round trip
-    // in front of the row gathers of the lane groups 1 .. G - 1: 2 300 cycles until the rows were there against 1 800 for one sample)
-    int4 slot_rec = make_int4(0, 0, 0, 0);
-    if constexpr (BPR && G > 1)
-        slot_rec = p.slot_recs[(size_t)batch_local * p.slot_rec_stride + (size_t)min(wv, p.tasks_per_batch - 1) * 3 + max(lane / LPR - 1, 0)];
     long long batch_base = 0;
     MuRequest<T> mu_req;
     mu_req.st = MuState<T>{};
@@ -136,16 +146,16 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
         batch_base = (&p.state->batch_base)[zero];
         mu_req = global_bias_request(p, (batch_local + 2) % 3 + zero, lane);
     }
-    // (the kernel arguments the row gathers need are requested now, next to the header, rather than in a second scalar
+    // (the table entries the row gathers need are requested now, next to the header, rather than in a second scalar
     // round trip after the header has arrived)
-    asm volatile("" ::"s"(p.k), "s"(p.U0), "s"(p.U1), "s"(p.V0), "s"(p.V1), "s"(p.recs));
+    if constexpr (!ARGS_HERE) asm volatile("" ::"s"(p.k), "s"(p.U0), "s"(p.U1), "s"(p.V0), "s"(p.V1), "s"(p.recs));
     if constexpr (BPR) {
         if (p.sgd_mode == MI355REC_ADAM) gb += p.state->batch_base;
     } else {
         gb += batch_base;
     }
     const int4 h0 = make_int4(hd[0], hd[1], hd[2], hd[3]), h1 = make_int4(hd[4], hd[5], hd[6], hd[7]);
-    const bool active = (h0.y & LEN_MASK) != 0 && wv < p.tasks_per_batch;
+    const bool active = (h0.y & LEN_MASK) != 0 && wv < tpb;
     __shared__ T s_mu[4];
     __shared__ T s_wide[4][LPR * KI * VEC];
     __shared__ T s_wide_bias[4];
@@ -376,7 +386,7 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
             if (sum != (T)0) atomicAdd(&p.mu_acc[(batch_local % 3) * MU_SLOTS + (wg & (MU_SLOTS - 1))], sum);
         }
     }
-    if (p.ticks && lane == 0 && wv < p.tasks_per_batch) {
+    if (p.ticks && lane == 0 && wv < tpb) {
         unsigned long long *o = p.ticks + (size_t)wv * 8;
         o[0] = tk0; o[1] = tk1; o[2] = tk2; o[3] = tk3; o[4] = stamp(); o[5] = (unsigned long long)(h0.y & LEN_MASK);
         o[6] = tk4; o[7] = tk5;
@@ -386,20 +396,22 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
 // PLAIN_SGD: the instance for sgd_mode == "sgd" (the reference's default, the headline): every branch on the optimiser is decided at
 // compile time.  The update of the item rows a pair task took over ran through 1 600 instructions of optimiser cases -- 1 730 cycles
 // of the 6 500 a wavefront lives (MI355REC_MF_TICKS, round 4).
+// The leading arguments are all the header's address is made of -- the mini-batch's headers (p.tasks + batch_local *
+// p.tasks_per_batch) and pair records by slot (p.slot_recs + batch_local * p.slot_rec_stride), p.tasks_per_batch, p.wg_base, p.wg_stride,
+// p.ticks != NULL: mf.hip is built with -amdgpu-kernarg-preload-count, which has them arrive in scalar registers with the wavefront
+// (a by-value struct is never preloaded), so the header is requested by the kernel's first instructions instead of behind a cold
+// fetch of the kernarg segment.  Where the firmware does not preload, the compiler's compatibility prologue loads the same registers.
 template <int ALGO, class T, int VEC, int LPR, int KI, bool PLAIN_SGD>
-__global__ __launch_bounds__(256) void mf_batch_kernel(const MfParams<T> p, const int batch_local) {
+__global__ __launch_bounds__(256) void mf_batch_kernel(const TaskHeader *hdr, const int4 *slot, const int tasks_per_batch, const int wg_base,
+                                                       const int wg_stride, const int stamps, const MfParams<T> p, const int batch_local) {
     // (an assumption about the argument, not a modified copy: a copy that is passed on by reference lands in scratch memory)
     if constexpr (PLAIN_SGD) __builtin_assume(p.sgd_mode == MI355REC_SGD);
-    // Every kernel argument the start of the kernel needs is requested in ONE batch of scalar loads: left to itself the compiler
-    // fetched them piecewise as the code came to need them -- three waits for a cold kernarg segment before FunkSVD's header load
-    // was even issued, one for BPR's.
-    asm volatile("" ::"s"(p.tasks), "s"(p.tasks_per_batch), "s"(p.wg_base), "s"(p.wg_stride), "s"(p.ticks), "s"(p.use_bias), "s"(p.sgd_mode),
-                 "s"(p.state), "s"(p.mu_state), "s"(p.mu_acc), "s"(p.k), "s"(p.U0), "s"(p.U1), "s"(p.V0), "s"(p.V1), "s"(p.recs));
-    // (here and not in the body: the group launch below reads its parameters from a table in memory, where holding them all in
-    // scalar registers from the start costs occupancy)
+    // (the ONE batched request for the other arguments sits in the body, behind the header's; the group launch below reads its
+    // parameters from a table in memory, where holding them all in scalar registers from the start costs occupancy)
     // (Measured and rejected, round 4: a launch over a third of the slots with a loop over the slots in use, as the group launch does --
     // BPR 198 against 196 M samples/s, FunkSVD, whose slots are nearly all in use, 102 against 161 M.)
-    mf_batch_body<ALGO, T, VEC, LPR, KI>(p, batch_local, blockIdx.x);
+    const int wv = __builtin_amdgcn_readfirstlane((blockIdx.x * wg_stride + wg_base) * 4 + (threadIdx.x >> 6));
+    mf_batch_body<ALGO, T, VEC, LPR, KI, true>(p, batch_local, blockIdx.x, wv, tasks_per_batch, hdr, slot, stamps != 0);
 }
 
 // REPLICA-BATCHED launch: mini-batch `batch_local` of R independent models in one grid (blockIdx.y = model).  A single model's
@@ -436,7 +448,12 @@ __global__ __launch_bounds__(256, (PLAIN_SGD && ALGO == MI355REC_MF_BPR && sizeo
     // the grid covers a third of a mini-batch's header slots; with fused / paired tasks fewer than that are in use as a rule
     // (the in-LDS schedule files the count), and a workgroup that finds more walks on: no wavefront is launched for an empty slot
     const int used = p.used ? p.used[batch_local] : p.tasks_per_batch;
-    for (int wg = blockIdx.x; wg * 4 < used; wg += gridDim.x) mf_batch_body<ALGO, T, VEC, LPR, KI>(p, batch_local, wg);
+    const TaskHeader *hdr = p.tasks + (size_t)batch_local * p.tasks_per_batch;
+    const int4 *slot = p.slot_recs + (size_t)batch_local * p.slot_rec_stride;
+    for (int wg = blockIdx.x; wg * 4 < used; wg += gridDim.x) {
+        const int wv = __builtin_amdgcn_readfirstlane((wg * p.wg_stride + p.wg_base) * 4 + (threadIdx.x >> 6));
+        mf_batch_body<ALGO, T, VEC, LPR, KI, false>(p, batch_local, wg, wv, p.tasks_per_batch, hdr, slot, p.ticks != nullptr);
+    }
 }
 // Sampler and schedule of every member in ONE launch each (model on the last grid dimension): as 4 x R small launches on R
 // streams they took a third of a 32-model epoch.
