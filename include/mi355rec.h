@@ -180,6 +180,9 @@ int mi355rec_sim_compute_csr(mi355rec_sim_t h, int32_t start_col, int32_t end_co
                              float *data, int64_t *nnz);
 /* topK == 0 variant (.pyx:507-510): W[j * ld + (c - start_col)] = similarity(j, c); W is host, row-major, ld >= end_col-start_col. */
 int mi355rec_sim_compute_dense(mi355rec_sim_t h, int32_t start_col, int32_t end_col, float *W, int64_t ld);
+/* The same columns left on the device: column c contiguous at d_W + (c - start_col) * ld (ld >= n_cols); nothing is downloaded.
+ * Returns after the handle's stream has drained. */
+int mi355rec_sim_compute_dense_device(mi355rec_sim_t h, int32_t start_col, int32_t end_col, float *d_W, int64_t ld);
 /* cost(c) = sum over users of column c of their profile length: the work of one column; used to cut
  * cost-balanced column ranges for multi-GPU sharding. */
 int mi355rec_sim_column_costs(mi355rec_sim_t h, int64_t *cost /* n_cols */);
@@ -490,6 +493,43 @@ int mi355rec_nmf_get_stats(mi355rec_nmf_t h, mi355rec_stats *stats);
 int mi355rec_nmf_fit_info(mi355rec_nmf_t h, double *phase_ms, int64_t *launches, int64_t *calls, int64_t *create_bytes, int64_t *h2d_bytes,
                           int64_t *d2h_bytes, int32_t *all_ones);
 void mi355rec_nmf_destroy(mi355rec_nmf_t h);
+
+/* ------------------------------------------------------------------------------------------------------
+ * EASE_R  (EASE_R/EASE_R_Recommender.py:40-82: W = P / (-diag P) with P = (X^T X + diag)^-1, then similarityMatrixTopK) -- the Gram
+ * matrix, its inverse, the weights and their column-wise top-K stay in HBM.  The device inverse is an
+ * unpivoted blocked elimination: it serves symmetric POSITIVE-DEFINITE matrices and refuses every other one.
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_ease *mi355rec_ease_t;
+
+/* An n_items x n_items float32 matrix on the device and the panel workspace of the elimination; MI355REC_E_INVALID, before anything
+ * is launched, when they do not fit the device's free memory. */
+int mi355rec_ease_create(mi355rec_ease_t *out, int32_t n_items);
+/* The matrix <- X^T X of a similarity handle built with topK == 0 (shrink 0, normalize 0, cosine), on the device; the diagonal is 0.
+ * A handle whose topK != 0 or whose n_cols != n_items is MI355REC_E_INVALID. */
+int mi355rec_ease_set_gram_from_sim(mi355rec_ease_t h, mi355rec_sim_t sim);
+/* Upload of any symmetric matrix (G[i * ld + j], host) / download of whatever the matrix currently holds. */
+int mi355rec_ease_set_matrix(mi355rec_ease_t h, const float *G, int64_t ld);
+int mi355rec_ease_get_matrix(mi355rec_ease_t h, float *G, int64_t ld);
+/* The diagonal <- diag (n_items floats); needs a matrix that has been set and not yet inverted. */
+int mi355rec_ease_set_diagonal(mi355rec_ease_t h, const float *diag);
+/* The matrix <- its inverse, in place.  MI355REC_E_NUMERIC when a pivot is <= 0 or NaN -- the matrix is not positive definite;
+ * mi355rec_last_error() names the step, the content of the matrix is then undefined and a new one has to be set. */
+int mi355rec_ease_invert(mi355rec_ease_t h);
+/* W[i * ld + j] = P[i][j] / -P[j][j], 0 on the diagonal (host, row-major).  Needs a successful invert, else MI355REC_E_INVALID. */
+int mi355rec_ease_get_dense(mi355rec_ease_t h, float *W, int64_t ld);
+/* Per column of W its topK largest NON-ZERO cells by value (similarityMatrixTopK, Base/Recommender_utils.py:55): idx / val
+ * [n_items][topK], value-descending, ties towards the lower row, (-1, 0) padded.  topK > 4096 or columns beyond the in-LDS selection
+ * (about 30 000 cells) are MI355REC_E_UNSUPPORTED. */
+int mi355rec_ease_get_topk(mi355rec_ease_t h, int32_t topK, int32_t *idx, float *val);
+/* Block size and number of steps of the elimination, the step that failed (-1: none), device milliseconds of the last invert, wall
+ * milliseconds of the last set_gram_from_sim, device milliseconds of the weights (+ top-K) kernels, kernel launches since the last
+ * invert. */
+int mi355rec_ease_fit_info(mi355rec_ease_t h, int32_t *block, int32_t *steps, int32_t *failed_step, double *invert_ms, double *gram_ms,
+                           double *topk_ms, int64_t *launches);
+/* Of the last invert: algorithmic_flops = 2 n^3, algorithmic_bytes = 8 n^2 per step. */
+int mi355rec_ease_get_stats(mi355rec_ease_t h, mi355rec_stats *stats);
+void mi355rec_ease_destroy(mi355rec_ease_t h);
 
 /* ------------------------------------------------------------------------------------------------------
  * Scoring + ranking of factor models  (Base/BaseMatrixFactorizationRecommender.py:38

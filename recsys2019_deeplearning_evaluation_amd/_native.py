@@ -88,6 +88,7 @@ SIGNATURES = {
     "mi355rec_sim_compute": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "mi355rec_sim_compute_device": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "mi355rec_sim_compute_dense": (C.c_int, [_vp, _i32, _i32, _vp, _i64]),
+    "mi355rec_sim_compute_dense_device": (C.c_int, [_vp, _i32, _i32, _vp, _i64]),
     "mi355rec_sim_compute_csr": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "mi355rec_sim_column_costs": (C.c_int, [_vp, _vp]),
     "mi355rec_sim_schedule_info": (C.c_int, [_vp, _vp, _vp, _vp]),
@@ -165,6 +166,18 @@ SIGNATURES = {
     "mi355rec_nmf_fit_info": (C.c_int, [_vp, C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
                                         C.POINTER(_i64), C.POINTER(_i32)]),
     "mi355rec_nmf_destroy": (None, [_vp]),
+    "mi355rec_ease_create": (C.c_int, [C.POINTER(_vp), _i32]),
+    "mi355rec_ease_set_gram_from_sim": (C.c_int, [_vp, _vp]),
+    "mi355rec_ease_set_matrix": (C.c_int, [_vp, _vp, _i64]),
+    "mi355rec_ease_get_matrix": (C.c_int, [_vp, _vp, _i64]),
+    "mi355rec_ease_set_diagonal": (C.c_int, [_vp, _vp]),
+    "mi355rec_ease_invert": (C.c_int, [_vp]),
+    "mi355rec_ease_get_dense": (C.c_int, [_vp, _vp, _i64]),
+    "mi355rec_ease_get_topk": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "mi355rec_ease_fit_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f64), C.POINTER(_f64),
+                                         C.POINTER(_f64), C.POINTER(_i64)]),
+    "mi355rec_ease_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
+    "mi355rec_ease_destroy": (None, [_vp]),
     "mi355rec_scorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),
     "mi355rec_scorer_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32]),
     "mi355rec_scorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

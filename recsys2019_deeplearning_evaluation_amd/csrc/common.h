@@ -252,4 +252,7 @@ void handle_destroy(H *h) {
     delete h;
 }
 
+// sim.hip: what another handle type (ease.hip) checks before it asks a similarity handle for its dense columns
+void sim_shape(const mi355rec_sim *h, int *n_cols, int *topK);
+
 }  // namespace mi355rec

@@ -1260,6 +1260,36 @@ extern "C" int mi355rec_sim_compute_dense(mi355rec_sim_t h, int32_t start_col, i
     });
 }
 
+extern "C" int mi355rec_sim_compute_dense_device(mi355rec_sim_t h, int32_t start_col, int32_t end_col, float *d_W, int64_t ld) {
+    return guarded([&] {
+        MI_REQUIRE(h && d_W, "NULL argument");
+        ensure_device();
+        clamp_range(h, start_col, end_col);
+        ReleaseScope scope(h->stream);
+        const int n_local = end_col - start_col;
+        MI_REQUIRE(ld >= h->n_cols, "ld (%lld) < length of a column (%d)", (long long)ld, h->n_cols);
+        if (ld == h->n_cols) {
+            run_columns(h, ColumnSelection::range(start_col, end_col), nullptr, nullptr, d_W);
+        } else {            // (the column kernel's own pitch is n_cols)
+            DeviceBuffer<float> slab;
+            slab.alloc((size_t)n_local * h->n_cols);
+            run_columns(h, ColumnSelection::range(start_col, end_col), nullptr, nullptr, slab.ptr);
+            MI_HIP(hipMemcpy2DAsync(d_W, (size_t)ld * sizeof(float), slab.ptr, (size_t)h->n_cols * sizeof(float),
+                                    (size_t)h->n_cols * sizeof(float), (size_t)n_local, hipMemcpyDeviceToDevice, h->stream));
+        }
+        MI_HIP(hipStreamSynchronize(h->stream));
+        read_timers(h);
+    });
+}
+
+namespace mi355rec {
+// what ease.hip checks before it asks a handle for its Gram matrix
+void sim_shape(const mi355rec_sim *h, int *n_cols, int *topK) {
+    *n_cols = h->n_cols;
+    *topK = h->cfg.topK;
+}
+}  // namespace mi355rec
+
 extern "C" int mi355rec_sim_column_costs(mi355rec_sim_t h, int64_t *cost) {
     return guarded([&] {
         MI_REQUIRE(h && cost, "NULL argument");

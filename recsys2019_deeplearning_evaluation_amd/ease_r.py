@@ -5,12 +5,23 @@ similarity="cosine")` for X^T X and densifies it.  Here the same product comes s
 (topK = 0) path.  What follows is the closed form of Steck's model, B = I - P diag(1 / diag P) with P = (X^T X + l2 I)^-1,
 evaluated like the reference does it: one float32 `np.linalg.inv` on the host (a third-party LAPACK solve, outside the
 hot path) and the division of every column by its own diagonal entry.
+
+`EASE_R_MI355X_Recommender` keeps the whole closed form on the device (csrc/ease.hip): the Gram matrix goes
+from the similarity handle straight into an `MI355XEase` handle, is inverted there in place by an unpivoted blocked elimination,
+scaled, and reduced to its column-wise top-K; only W (or its top-K slabs) is downloaded.  That elimination is for positive-definite
+matrices -- every binary or normalised URM -- and says so when the matrix is not (explicit ratings: the reference puts the
+number of stored cells, not the sum of squares, on the diagonal); the fit then finishes with the host inverse of the class above.
 """
+import ctypes as C
+import time
+
 import numpy as np
 import scipy.sparse as sps
 
+from . import _native as N
 from .recommender_base import BaseItemSimilarityMatrixRecommender, similarityMatrixTopK
-from .similarity import Compute_Similarity_MI355X
+from .scoring import GpuSimilarityScoringMixin, _ScoringMixin
+from .similarity import Compute_Similarity_MI355X, slabs_to_csr
 
 
 def _unit_l2(X, axis):
@@ -68,3 +79,143 @@ class EASE_R_Recommender(BaseItemSimilarityMatrixRecommender):
         masked = np.full(scores.shape, -np.inf, dtype=np.float32)
         masked[:, items_to_compute] = scores[:, items_to_compute]
         return masked
+
+
+class MI355XEase(N.Handle):
+    """An n_items x n_items float32 matrix in HBM with the steps of the closed form: fill, invert in place (symmetric
+    positive-definite input only: anything else raises FloatingPointError), weights, column-wise top-K."""
+    _PREFIX = "mi355rec_ease"
+
+    def __init__(self, n_items):
+        self.n_items = int(n_items)
+        self._create(self.n_items)
+
+    def set_gram_from(self, similarity):
+        """The matrix <- X^T X (zero diagonal) of a `Compute_Similarity_MI355X` built with topK=0, shrink=0, normalize=False; nothing
+        crosses PCIe."""
+        if not similarity._h:
+            raise ValueError("the similarity handle is closed")
+        self._call("set_gram_from_sim", similarity._h)
+
+    def _square(self, G):
+        G = N.as_f32(G)
+        if G.shape != (self.n_items, self.n_items):
+            raise ValueError("the matrix must be %d x %d, got %r" % (self.n_items, self.n_items, G.shape))
+        return G
+
+    def set_matrix(self, G):
+        G = self._square(G)
+        self._call("set_matrix", N.ptr(G), self.n_items)
+
+    def get_matrix(self):
+        G = np.empty((self.n_items, self.n_items), np.float32)
+        self._call("get_matrix", N.ptr(G), self.n_items)
+        return G
+
+    def set_diagonal(self, diagonal):
+        d = N.as_f32(diagonal)
+        if d.shape != (self.n_items,):
+            raise ValueError("the diagonal must have %d entries, got %r" % (self.n_items, d.shape))
+        self._call("set_diagonal", N.ptr(d))
+
+    def invert(self):
+        self._call("invert")
+
+    def get_dense(self):
+        """W = P / (-diag P) with a zero diagonal, float32 (n_items, n_items)."""
+        W = np.empty((self.n_items, self.n_items), np.float32)
+        self._call("get_dense", N.ptr(W), self.n_items)
+        return W
+
+    def get_topk(self, topK):
+        """(idx int32, val float32) of shape (n_items, topK): per column of W its topK largest non-zero cells, value-descending,
+        (-1, 0) padded.  NotImplementedError where the column or topK is beyond the in-LDS selection."""
+        topK = int(topK)
+        idx = np.empty((self.n_items, max(topK, 0)), np.int32)
+        val = np.empty((self.n_items, max(topK, 0)), np.float32)
+        self._call("get_topk", topK, N.ptr(idx), N.ptr(val))
+        return idx, val
+
+    def fit_info(self):
+        i = [C.c_int32() for _ in range(3)]
+        ms = [C.c_double() for _ in range(3)]
+        launches = C.c_int64()
+        self._call("fit_info", *[C.byref(x) for x in i + ms], C.byref(launches))
+        return {"block": i[0].value, "steps": i[1].value, "failed_step": i[2].value, "invert_ms": ms[0].value, "gram_ms": ms[1].value,
+                "topk_ms": ms[2].value, "launches": launches.value}
+
+
+class _EASELogic:
+    """Drop-in for the reference's EASE_R_Recommender (EASE_R_Recommender.py:20) with the same `fit(topK=None, l2_norm=1e3,
+    normalize_matrix=False, verbose=True)` and the same `W_sparse` (float32 ndarray when topK is None, otherwise a csr_matrix).
+    `fit_info` says where the inverse ran ("device", or "host" with the reason and the elimination step that refused)."""
+
+    RECOMMENDER_NAME = "EASE_R_MI355X_Recommender"         # (saved models and logs tell the two classes apart)
+
+    def __init__(self, URM_train, verbose=True):
+        super(_EASELogic, self).__init__(URM_train, verbose=verbose)
+
+    def fit(self, topK=None, l2_norm=1e3, normalize_matrix=False, verbose=True):
+        self.verbose = verbose
+        if normalize_matrix:                    # unit rows first, then unit columns of the result (:47-51)
+            self.URM_train = sps.csr_matrix(_unit_l2(_unit_l2(self.URM_train, axis=1), axis=0))
+        n_items = self.URM_train.shape[1]
+        # the diagonal of X^T X is taken as the number of stored cells of each item (:63), plus the ridge term
+        diagonal = (np.diff(self.URM_train.tocsc().indptr) + l2_norm).astype(np.float32)
+        t_start = time.perf_counter()
+        builder = Compute_Similarity_MI355X(self.URM_train, topK=0, shrink=0, normalize=False, similarity="cosine")
+        ease = None
+        try:
+            ease = MI355XEase(n_items)
+            ease.set_gram_from(builder)
+            self.similarity_stats = builder.stats()
+            ease.set_diagonal(diagonal)
+            t_filled = time.perf_counter()
+            try:
+                ease.invert()
+                info = dict(ease.fit_info(), inverse="device", reason="")
+                t_inverted = time.perf_counter()
+                weights = None
+                if topK is not None:
+                    try:
+                        idx, val = ease.get_topk(min(int(topK), n_items))
+                        self.W_sparse = slabs_to_csr(idx, val, 0, n_items)
+                    except NotImplementedError:         # a column or a topK beyond the in-LDS selection: rank the dense W on the host
+                        weights = ease.get_dense()
+                else:
+                    self.W_sparse = ease.get_dense()
+                info["topk_ms"] = ease.fit_info()["topk_ms"]
+            except FloatingPointError as exc:
+                # not positive definite.  The failed elimination has destroyed the matrix: the Gram matrix is built again (milliseconds)
+                # instead of keeping a second n x n copy, and the reference's pivoted float32 inverse finishes on the host
+                info = dict(ease.fit_info(), inverse="host", reason=str(exc))
+                ease.set_gram_from(builder)
+                ease.set_diagonal(diagonal)
+                gram = ease.get_matrix()
+                precision = np.linalg.inv(gram)
+                weights = precision / -precision.diagonal()              # column j over -P[j, j]
+                weights.flat[::n_items + 1] = 0.0
+                t_inverted = time.perf_counter()
+                if topK is None:
+                    self.W_sparse, weights = weights, None
+            if weights is not None:
+                self.W_sparse = sps.csr_matrix(similarityMatrixTopK(weights, k=topK, verbose=False))
+        finally:
+            if ease is not None:
+                ease.close()
+            builder.close()
+        info.update(fill_s=t_filled - t_start, invert_s=t_inverted - t_filled, finish_s=time.perf_counter() - t_inverted)
+        self.fit_info = info
+
+    def recommend(self, user_id_array, *args, **kwargs):
+        """The device sparse scorer for a sparse W_sparse; the dense array of topK=None is scored by the recommender base on the host
+         -- the device mixin, where the class has one, is stepped over."""
+        if isinstance(self, _ScoringMixin) and not self.device_scorable():
+            return super(_ScoringMixin, self).recommend(user_id_array, *args, **kwargs)
+        return super(_EASELogic, self).recommend(user_id_array, *args, **kwargs)
+
+    _compute_item_score = EASE_R_Recommender._compute_item_score
+
+
+class EASE_R_MI355X_Recommender(_EASELogic, GpuSimilarityScoringMixin, BaseItemSimilarityMatrixRecommender):
+    pass

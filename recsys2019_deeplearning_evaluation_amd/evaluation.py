@@ -217,7 +217,7 @@ class EvaluatorHoldout_MI355X(N.Handle):
         block = int(block_size) if block_size else self._block_size()
         if isinstance(rec, GpuScoringMixin):
             self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
-        elif isinstance(rec, GpuSimilarityScoringMixin):
+        elif isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
         else:
             self._run_lists(rec, block)
@@ -316,7 +316,7 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
         n_eval = len(self.users_to_evaluate)
         if self.candidates_on_device and isinstance(rec, GpuScoringMixin):
             self._run_fused(rec._get_scorer(), "add_scorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
-        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin):
+        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer_candidates", rec, int(block_size) if block_size else self._block_size())
         else:
             self._run_lists(rec, int(block_size) if block_size else self._block_size())

@@ -19,6 +19,7 @@ the package works where the reference tree is not importable.  Inside the refere
 """
 from types import SimpleNamespace
 
+from .ease_r import _EASELogic
 from .graph_based import _P3alphaLogic, _RP3betaLogic
 from .ials import _IALSLogic
 from .knn import _ItemKNNLogic, _UserKNNLogic
@@ -45,6 +46,7 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         "SLIMElasticNetRecommender": (_SLIMElasticNetLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "PureSVDRecommender": (_PureSVDLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
         "PureSVDItemRecommender": (_PureSVDItemLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
+        "EASE_R_MI355X_Recommender": (_EASELogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "NMFRecommender": (_NMFLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
         "ItemKNNCFRecommender": (_ItemKNNLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "UserKNNCFRecommender": (_UserKNNLogic,) + sim_score + (BaseUserSimilarityMatrixRecommender,),

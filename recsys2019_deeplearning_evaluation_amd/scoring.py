@@ -206,6 +206,11 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
     _sp_scorer_src = None
     _SCORER_ATTRS = ("_sp_scorer", "_sp_scorer_src")
 
+    def device_scorable(self):
+        """False while W_sparse is a dense array (EASE_R with topK=None keeps the reference's ndarray): the sparse scorer takes a CSR, so
+        such a model is scored by the base class on the host -- its own recommend() and the device evaluators' lists path."""
+        return not isinstance(getattr(self, "W_sparse", None), np.ndarray)
+
     def _get_sparse_scorer(self):
         # strong references + identity (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of
         # the first, freed matrix can be handed to its successor, so an id() key would score with stale weights)
