@@ -212,6 +212,32 @@ int mi355rec_sim_get_stats(mi355rec_sim_t h, mi355rec_stats *stats);
 void mi355rec_sim_destroy(mi355rec_sim_t h);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Stacking CSR matrices that are already in device memory (csrc/stack.hip): the dataMatrix of the CF+CBF hybrid KNN
+ * recommenders (KNN/ItemKNN_CFCBF_Hybrid_Recommender.py:20-25: hstack([ICM_train * ICM_weight, URM_train.T]), built on its
+ * transpose) is a few feature rows on top of the user rows.  The blocks stay resident for a whole search; only the weight changes
+ * from fit to fit, so the stack is made in HBM and handed to mi355rec_sim_create_resident.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t n_rows;             /* rows of the block (0 is allowed) */
+    int32_t nnz;                /* stored cells of the block */
+    const int32_t *d_indptr;    /* n_rows + 1 row pointers starting at 0 (device) */
+    const int32_t *d_indices;   /* nnz column ids in [0, n_cols) (device; may be NULL when nnz == 0) */
+    const float *d_data;        /* nnz values (device; may be NULL when nnz == 0) */
+    float scale;                /* every value of the block is multiplied by it, one float32 product (NumPy's `data * w` of a
+                                 * float32 array); exactly 1 copies the bits */
+} mi355rec_csr_block;
+
+#define MI355REC_STACK_MAX_BLOCKS 16
+
+/* d_indptr (total rows + 1), d_indices and d_data (total cells each): the CSR of the blocks' rows one after the other -- row
+ * pointers offset by the cells of the blocks before, indices copied, values scaled.  One launch for all blocks and arrays; returns
+ * after it has run.  Checked on the host before anything touches the device (MI355REC_E_INVALID): n_blocks < 1, NULL arguments,
+ * negative sizes, total rows or total cells beyond int32; more than MI355REC_STACK_MAX_BLOCKS blocks is MI355REC_E_UNSUPPORTED.  A
+ * column id outside [0, n_cols) found while copying is MI355REC_E_INVALID as well (the outputs are then not to be used). */
+int mi355rec_csr_stack_device(int32_t n_blocks, const mi355rec_csr_block *blocks, int32_t n_cols, int32_t *d_indptr,
+                              int32_t *d_indices, float *d_data);
+
+/* ------------------------------------------------------------------------------------------------------
  * Matrix-factorisation SGD epochs  (MatrixFactorization/Cython/MatrixFactorization_Cython_Epoch.pyx:50
  * cdef class MatrixFactorization_Cython_Epoch; __init__ :95-148; epochIteration_Cython :273;
  * get_USER_factors ... get_GLOBAL_bias :685-702)

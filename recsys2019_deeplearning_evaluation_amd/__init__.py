@@ -5,9 +5,11 @@ Hot path only: Compute_Similarity (ItemKNN build), BPR-MF 
 IALS solve step, SLIM ElasticNet coordinate descent, PureSVD's randomized SVD, NMF's coordinate-descent and multiplicative-update solvers.  Python host code + ctypes C-ABI (include/mi355rec.h) + hand-written HIP kernels (csrc/).
 Nothing here imports torch; torch.distributed is only used by `sharding` for the multi-GPU gather.
 """
-from ._native import ResidentURM  # noqa: F401
+from ._native import ResidentURM, ResidentStack  # noqa: F401
 from .similarity import Compute_Similarity, Compute_Similarity_MI355X, Compute_Similarity_Euclidean_MI355X  # noqa: F401
 from .knn import ItemKNNCFRecommender, UserKNNCFRecommender  # noqa: F401
+from .knn_cbf import (ItemKNNCBFRecommender, UserKNNCBFRecommender, ItemKNN_CFCBF_Hybrid_Recommender,  # noqa: F401
+                      UserKNN_CFCBF_Hybrid_Recommender, ItemKNNCustomSimilarityRecommender)
 from .matrix_factorization import (MatrixFactorization_MI355X_Epoch, MatrixFactorization_BPR_MI355X,  # noqa: F401
                                    MatrixFactorization_FunkSVD_MI355X, MatrixFactorization_AsySVD_MI355X,
                                    MatrixFactorization_MI355X_Group)
@@ -22,5 +24,5 @@ from .evaluation import EvaluatorHoldout_MI355X, EvaluatorNegativeItemSample_MI3
 from .pure_svd import PureSVDRecommender, PureSVDItemRecommender  # noqa: F401,E402
 from .nmf import NMFRecommender  # noqa: F401,E402
 
-__all__ = ["ResidentURM", "PureSVDRecommender", "PureSVDItemRecommender", "NMFRecommender", "EvaluatorHoldout_MI355X", "EvaluatorNegativeItemSample_MI355X", "EASE_R_Recommender", "EASE_R_MI355X_Recommender", "MI355XEase", "SLIMElasticNetRecommender", "P3alphaRecommender", "RP3betaRecommender", "MI355XScorer", "MI355XSparseScorer", "GpuScoringMixin", "GpuSimilarityScoringMixin", "SLIM_BPR_MI355X_Epoch", "SLIM_BPR_MI355X", "IALS_MI355X_Epoch", "IALSRecommender", "Compute_Similarity", "Compute_Similarity_MI355X", "Compute_Similarity_Euclidean_MI355X", "ItemKNNCFRecommender", "UserKNNCFRecommender",
+__all__ = ["ResidentURM", "ResidentStack", "ItemKNNCBFRecommender", "UserKNNCBFRecommender", "ItemKNN_CFCBF_Hybrid_Recommender", "UserKNN_CFCBF_Hybrid_Recommender", "ItemKNNCustomSimilarityRecommender", "PureSVDRecommender", "PureSVDItemRecommender", "NMFRecommender", "EvaluatorHoldout_MI355X", "EvaluatorNegativeItemSample_MI355X", "EASE_R_Recommender", "EASE_R_MI355X_Recommender", "MI355XEase", "SLIMElasticNetRecommender", "P3alphaRecommender", "RP3betaRecommender", "MI355XScorer", "MI355XSparseScorer", "GpuScoringMixin", "GpuSimilarityScoringMixin", "SLIM_BPR_MI355X_Epoch", "SLIM_BPR_MI355X", "IALS_MI355X_Epoch", "IALSRecommender", "Compute_Similarity", "Compute_Similarity_MI355X", "Compute_Similarity_Euclidean_MI355X", "ItemKNNCFRecommender", "UserKNNCFRecommender",
            "MatrixFactorization_MI355X_Epoch", "MatrixFactorization_MI355X_Group", "MatrixFactorization_BPR_MI355X", "MatrixFactorization_FunkSVD_MI355X", "MatrixFactorization_AsySVD_MI355X"]

@@ -63,6 +63,14 @@ class SlimConfig(C.Structure):
                 ("precision", C.c_int32), ("train_with_sparse_weights", C.c_int32), ("topK", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CsrBlock(C.Structure):
+    """mi355rec_csr_block: one resident CSR matrix of a stack and the factor its values are multiplied by."""
+    _fields_ = [("n_rows", C.c_int32), ("nnz", C.c_int32), ("d_indptr", C.c_void_p), ("d_indices", C.c_void_p), ("d_data", C.c_void_p),
+                ("scale", C.c_float)]
+
+
+STACK_MAX_BLOCKS = 16
+
 _vp = C.c_void_p
 _i32, _i64, _f32, _f64 = C.c_int32, C.c_int64, C.c_float, C.c_double
 
@@ -98,6 +106,7 @@ SIGNATURES = {
     "mi355rec_sim_sync": (C.c_int, [_vp]),
     "mi355rec_sim_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_sim_destroy": (None, [_vp]),
+    "mi355rec_csr_stack_device": (C.c_int, [_i32, C.POINTER(CsrBlock), _i32, _vp, _vp, _vp]),
     "mi355rec_mf_create": (C.c_int, [C.POINTER(_vp), C.POINTER(MFConfig), _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mi355rec_mf_run_epochs": (C.c_int, [_vp, _i32]),
     "mi355rec_mf_run_samples": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
@@ -360,28 +369,18 @@ class DeviceArray:
             pass
 
 
-class ResidentURM:
-    """A CSR matrix (int32 structure, float32 values, sorted indices) uploaded ONCE to the calling process's GPU.  Similarity
-    builds started from it (`Compute_Similarity_MI355X(..., resident=...)`, `ItemKNNCFRecommender.fit(..., resident_urm=...)`)
-    copy the arrays at HBM speed instead of paying the PCIe upload in every fit -- the reference's hyper-parameter search runs
-    hundreds of fits on the same URM_train (ParameterTuning/SearchAbstractClass.py:253-262)."""
+class _HostIdentity:
+    """Which host CSR matrix is this?  Remembers one (its arrays are shared, not copied: the addresses of its three buffers are
+    part of its identity) and recognises it, or an equal copy, when it is presented again: `matches`."""
 
-    def __init__(self, matrix):
-        import scipy.sparse as sps
-        csr = sps.csr_matrix(matrix, dtype=np.float32)
-        if not csr.has_sorted_indices:
-            csr = csr.sorted_indices()
-        self.shape = csr.shape
+    def __init__(self, csr):
         self.nnz = int(csr.nnz)
         self._fingerprint = self.fingerprint_of(csr)
         self._buffers = self._buffers_of(csr)
         self._host = csr                         # (keeps the buffers alive: their addresses identify the matrix)
         self._full = None
-        self.indptr, self.indices, self.data = DeviceArray(len(csr.indptr)), DeviceArray(max(1, self.nnz)), DeviceArray(max(1, self.nnz))
-        lib = load()
-        for dev, host in ((self.indptr, as_i32(csr.indptr)), (self.indices, as_i32(csr.indices)), (self.data, as_f32(csr.data))):
-            if len(host):
-                check(lib.mi355rec_device_memcpy(dev.ptr, ptr(host), 4 * len(host), 1))
+        self._verified = {}
+        self._calls = 0
 
     @staticmethod
     def fingerprint_of(csr):
@@ -412,7 +411,7 @@ class ResidentURM:
         """A strided sample of indices and values of `csr` against the same positions of the uploaded matrix; the offset moves on
         with every call, so that repeated fits look at different entries (8192 per array and call)."""
         stride = max(1, self.nnz // 8192)
-        self._calls = getattr(self, "_calls", 0) + 1
+        self._calls += 1
         at = (self._calls * 2654435761) % stride
         mine = self._host
         return (np.array_equal(np.asarray(csr.indices)[at::stride], mine.indices[at::stride]) and
@@ -437,7 +436,7 @@ class ResidentURM:
             thorough = True if mode == "full" else (False if mode == "sample" else None)
         if thorough is False:
             return True
-        seen = self.__dict__.setdefault("_verified", {})
+        seen = self._verified
         if thorough is None and key in seen:
             return seen[key]
         if self._full is None:
@@ -447,6 +446,113 @@ class ResidentURM:
             seen.clear()
         seen[key] = verdict
         return verdict
+
+
+class ResidentURM:
+    """A CSR matrix (int32 structure, float32 values, sorted indices) uploaded ONCE to the calling process's GPU.  Similarity
+    builds started from it (`Compute_Similarity_MI355X(..., resident=...)`, `ItemKNNCFRecommender.fit(..., resident_urm=...)`)
+    copy the arrays at HBM speed instead of paying the PCIe upload in every fit -- the reference's hyper-parameter search runs
+    hundreds of fits on the same URM_train (ParameterTuning/SearchAbstractClass.py:253-262)."""
+
+    def __init__(self, matrix):
+        import scipy.sparse as sps
+        csr = sps.csr_matrix(matrix, dtype=np.float32)
+        if not csr.has_sorted_indices:
+            csr = csr.sorted_indices()
+        self.shape = csr.shape
+        self.nnz = int(csr.nnz)
+        self._host = csr
+        self._identity = _HostIdentity(csr)
+        # A CSC input is the transpose of a CSR matrix its owner keeps (`ICM_train.T`, `URM_train.T`: same three buffers): that
+        # matrix is remembered too, so that `matches_transposed` recognises it without a transposition per fit -- one more sampled
+        # fingerprint here, no copy.  (Like `_host` for a sorted float32 CSR input it shares the owner's arrays: a matrix edited in
+        # place after the upload is not the uploaded matrix any more, whichever of the two is asked.)
+        self._transposed = _HostIdentity(sps.csr_matrix(matrix.T, dtype=np.float32)) if sps.isspmatrix_csc(matrix) else None
+        self.indptr, self.indices, self.data = DeviceArray(len(csr.indptr)), DeviceArray(max(1, self.nnz)), DeviceArray(max(1, self.nnz))
+        lib = load()
+        for dev, host in ((self.indptr, as_i32(csr.indptr)), (self.indices, as_i32(csr.indices)), (self.data, as_f32(csr.data))):
+            if len(host):
+                check(lib.mi355rec_device_memcpy(dev.ptr, ptr(host), 4 * len(host), 1))
+
+    # ---- which host matrix this is: `_HostIdentity` above; the names below are this class's long-standing surface
+    fingerprint_of = staticmethod(_HostIdentity.fingerprint_of)
+    _buffers_of = staticmethod(_HostIdentity._buffers_of)
+
+    @property
+    def _verified(self):
+        return self._identity._verified
+
+    def matches(self, csr, thorough=None):
+        """Is `csr` the uploaded matrix?  See `_HostIdentity.matches`."""
+        return self._identity.matches(csr, thorough)
+
+    def matches_transposed(self, csr, thorough=None):
+        """Is the uploaded matrix the transpose of `csr`?  Answered for an object made from a CSC matrix (`ResidentURM(M.T)` of a CSR
+        M): `csr` is compared with that M exactly as `matches` compares with the uploaded matrix -- no transposition."""
+        return self._transposed is not None and self._transposed.matches(csr, thorough)
+
+    # ---- what a ResidentStack asks of its blocks
+    def value_range(self):
+        """(smallest, largest) stored value, (0, 0) for an empty matrix; one pass over the host copy, remembered."""
+        if getattr(self, "_range", None) is None:
+            d = self._host.data
+            self._range = (float(d.min()), float(d.max())) if len(d) else (0.0, 0.0)
+        return self._range
+
+    def count_non_finite(self):
+        return int(np.sum(np.logical_not(np.isfinite(self._host.data))))
+
+    def close(self):
+        for a in (self.indptr, self.indices, self.data):
+            a.close()
+
+
+class ResidentStack:
+    """`ResidentURM` blocks stacked row-wise into one CSR matrix IN device memory, block b's values multiplied by scales[b]
+    (mi355rec_csr_stack_device): bit for bit the arrays of `scipy.sparse.vstack([b * s ...], format="csr")`.  The dataMatrix of the CF+CBF
+    hybrid KNN recommenders -- feature rows times ICM_weight on top of the user rows -- made at HBM speed for every fit of a search,
+    from blocks that were uploaded once.  `indptr`, `indices`, `data` are DeviceArrays; `download()` returns the host CSR."""
+
+    def __init__(self, blocks, scales):
+        blocks, scales = list(blocks), [float(s) for s in scales]
+        if not blocks or len(blocks) != len(scales):
+            raise ValueError("ResidentStack: %d blocks and %d scales" % (len(blocks), len(scales)))
+        n_cols = blocks[0].shape[1]
+        if any(b.shape[1] != n_cols for b in blocks):
+            raise ValueError("ResidentStack: the blocks have different numbers of columns: {}".format([b.shape for b in blocks]))
+        n_rows, nnz = sum(b.shape[0] for b in blocks), sum(b.nnz for b in blocks)
+        if n_rows >= 2 ** 31 - 1 or nnz > 2 ** 31 - 1:
+            raise ValueError("ResidentStack: %d rows and %d cells do not fit int32 row pointers" % (n_rows, nnz))
+        self.blocks, self.scales = blocks, scales
+        self.shape, self.nnz = (n_rows, n_cols), nnz
+        self.indptr, self.indices, self.data = DeviceArray(n_rows + 1), DeviceArray(max(1, nnz)), DeviceArray(max(1, nnz))
+        table = (CsrBlock * len(blocks))(*[CsrBlock(b.shape[0], b.nnz, b.indptr.ptr, b.indices.ptr, b.data.ptr, s)
+                                           for b, s in zip(blocks, scales)])
+        check(load().mi355rec_csr_stack_device(len(blocks), table, n_cols, self.indptr.ptr, self.indices.ptr, self.data.ptr))
+
+    def structure(self):
+        """(indptr, indices) as host arrays, read back from the device copy."""
+        indptr = self.indptr.to_host()
+        return indptr, (self.indices.to_host()[:self.nnz] if self.nnz else np.empty(0, np.int32))
+
+    def download(self):
+        """The stacked matrix as a host CSR (float32, the blocks' sorted indices)."""
+        import scipy.sparse as sps
+        indptr, indices = self.structure()
+        data = self.data.to_host()[:self.nnz].view(np.float32) if self.nnz else np.empty(0, np.float32)
+        return sps.csr_matrix((data, indices, indptr), shape=self.shape)
+
+    def values_nonnegative(self):
+        """No stored value of the stack is negative -- from the blocks' value ranges and the signs of the scales, nothing is read back."""
+        for b, s in zip(self.blocks, self.scales):
+            lo, hi = b.value_range()
+            if (s > 0 and lo < 0) or (s < 0 and hi > 0):
+                return False
+        return True
+
+    def count_non_finite(self):
+        """For the message of the reference's assertion (a block under a non-finite scale counts whole)."""
+        return sum(b.count_non_finite() if np.isfinite(s) else b.nnz for b, s in zip(self.blocks, self.scales))
 
     def close(self):
         for a in (self.indptr, self.indices, self.data):

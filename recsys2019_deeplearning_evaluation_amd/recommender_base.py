@@ -6,6 +6,7 @@ Mirrors (same method names, argument meaning and error behaviour):
   BaseMatrixFactorizationRecommender  Base/BaseMatrixFactorizationRecommender.py:15  (_compute_item_score :38, save_model :81)
   BaseItemSimilarityMatrixRecommender Base/BaseSimilarityMatrixRecommender.py:69     (_compute_item_score :73)
   BaseUserSimilarityMatrixRecommender Base/BaseSimilarityMatrixRecommender.py:97
+  BaseItemCBFRecommender / BaseUserCBFRecommender  Base/BaseCBFRecommender.py:15 / :43
   Incremental_Training_Early_Stopping Base/Incremental_Training_Early_Stopping.py:15 (_train_with_early_stopping :91)
   check_matrix / similarityMatrixTopK Base/Recommender_utils.py:13 / :55
 
@@ -257,6 +258,42 @@ class BaseRecommender(object):
                         value[key] = item
             return True, value
         return False, None
+
+
+def _content_matrix(recommender, name, matrix, n_entities, entity):
+    """The private float32 CSR copy a content-based recommender keeps of the ICM / UCM it is given (one row per item / user, stored
+    zeros dropped) and the mask of the rows that hold nothing.  float32 whatever the caller's dtype: the device works on float32
+    values, and the hybrids' device stack is bit-identical to the host's only for a float32 product."""
+    if matrix.shape[0] != n_entities:
+        raise AssertionError("{}: {} has {} rows for the {} {}s of URM_train".format(
+            recommender.RECOMMENDER_NAME, name, matrix.shape[0], n_entities, entity))
+    own = sps.csr_matrix(matrix, dtype=np.float32, copy=True)
+    own.eliminate_zeros()
+    empty = own.getnnz(axis=1) == 0
+    if empty.any():
+        recommender._print("{}: {} of {} {}s ({:.2f} %) have no features".format(name, int(empty.sum()), n_entities, entity,
+                                                                              100.0 * empty.sum() / n_entities))
+    return own, empty
+
+
+class BaseItemCBFRecommender(BaseRecommender):
+    """A recommender that is also given an item content matrix, ICM_train (n_items x n_features) -- the role of
+    Base/BaseCBFRecommender.py:15.  Provides `ICM_train`, `n_features` and `_cold_item_CBF_mask` (items without any feature)."""
+
+    def __init__(self, URM_train, ICM_train, verbose=True):
+        super(BaseItemCBFRecommender, self).__init__(URM_train, verbose=verbose)
+        self.ICM_train, self._cold_item_CBF_mask = _content_matrix(self, "ICM_train", ICM_train, self.n_items, "item")
+        self.n_features = self.ICM_train.shape[1]
+
+
+class BaseUserCBFRecommender(BaseRecommender):
+    """The same for a user content matrix, UCM_train (n_users x n_features) -- the role of Base/BaseCBFRecommender.py:43.
+    Provides `UCM_train`, `n_features` and `_cold_user_CBF_mask` (users without any feature)."""
+
+    def __init__(self, URM_train, UCM_train, verbose=True):
+        super(BaseUserCBFRecommender, self).__init__(URM_train, verbose=verbose)
+        self.UCM_train, self._cold_user_CBF_mask = _content_matrix(self, "UCM_train", UCM_train, self.n_users, "user")
+        self.n_features = self.UCM_train.shape[1]
 
 
 class BaseMatrixFactorizationRecommender(BaseRecommender):

@@ -15,6 +15,9 @@ the package works where the reference tree is not importable.  Inside the refere
              Incremental_Training_Early_Stopping)
     rec = R.MatrixFactorization_BPR_MI355X(URM_train); rec.fit(epochs=300, num_factors=128, ...)
 
+`bind(..., BaseItemCBFRecommender=..., BaseUserCBFRecommender=...)` (`Base.BaseCBFRecommender`) adds the content-based and hybrid KNN
+recommenders and ItemKNNCustomSimilarityRecommender to the namespace.
+
 `device_scoring=False` leaves `recommend()` to the reference's own host implementation (Base/BaseRecommender.py:131).
 """
 from types import SimpleNamespace
@@ -23,6 +26,8 @@ from .ease_r import _EASELogic
 from .graph_based import _P3alphaLogic, _RP3betaLogic
 from .ials import _IALSLogic
 from .knn import _ItemKNNLogic, _UserKNNLogic
+from .knn_cbf import (_ItemKNNCBFLogic, _ItemKNNCFCBFHybridLogic, _ItemKNNCustomSimilarityLogic, _UserKNNCBFLogic,
+                      _UserKNNCFCBFHybridLogic)
 from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
 from .nmf import _NMFLogic
 from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
@@ -32,8 +37,10 @@ from .slim_elasticnet import _SLIMElasticNetLogic
 
 
 def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender, BaseUserSimilarityMatrixRecommender,
-         Incremental_Training_Early_Stopping, device_scoring=True):
-    """Returns a namespace with every recommender of this package rebuilt on the given (reference) base classes."""
+         Incremental_Training_Early_Stopping, device_scoring=True, BaseItemCBFRecommender=None, BaseUserCBFRecommender=None):
+    """Returns a namespace with every recommender of this package rebuilt on the given (reference) base classes.  The content-based
+    and hybrid KNN recommenders need `Base.BaseCBFRecommender`'s two classes as well: they are rebuilt when BaseItemCBFRecommender and
+    BaseUserCBFRecommender are given (ItemKNNCustomSimilarityRecommender with the item pair)."""
     mf_score = (GpuScoringMixin,) if device_scoring else ()
     sim_score = (GpuSimilarityScoringMixin,) if device_scoring else ()
     mf = mf_score + (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
@@ -53,4 +60,13 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         "P3alphaRecommender": (_P3alphaLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "RP3betaRecommender": (_RP3betaLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
     }
+    if BaseItemCBFRecommender is not None:
+        item_cbf = sim_score + (BaseItemCBFRecommender, BaseItemSimilarityMatrixRecommender)
+        table["ItemKNNCBFRecommender"] = (_ItemKNNCBFLogic,) + item_cbf
+        table["ItemKNN_CFCBF_Hybrid_Recommender"] = (_ItemKNNCFCBFHybridLogic,) + item_cbf
+        table["ItemKNNCustomSimilarityRecommender"] = (_ItemKNNCustomSimilarityLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,)
+    if BaseUserCBFRecommender is not None:
+        user_cbf = sim_score + (BaseUserCBFRecommender, BaseUserSimilarityMatrixRecommender)
+        table["UserKNNCBFRecommender"] = (_UserKNNCBFLogic,) + user_cbf
+        table["UserKNN_CFCBF_Hybrid_Recommender"] = (_UserKNNCFCBFHybridLogic,) + user_cbf
     return SimpleNamespace(**{name: type(name, bases, {"__doc__": bases[0].__doc__}) for name, bases in table.items()})

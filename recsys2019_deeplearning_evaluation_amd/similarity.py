@@ -44,6 +44,63 @@ class Compute_Similarity_MI355X(N.Handle):
         uploaded values; `weighted_matrix()` hands the re-weighted matrix back.  resident: a `_native.ResidentURM` holding THIS
         dataMatrix on the device (checked): the constructor copies it there instead of uploading it.  Not arguments of the
         reference class."""
+        self._check_arguments(similarity, feature_weighting, weighting_documents, K1, B)
+        if feature_weighting == "TF-IDF":
+            assert np.all(dataMatrix.data >= 0.0), \
+                "TF_IDF: Data matrix contains {} negative values, computing the square root is not possible.".format(np.sum(dataMatrix.data < 0.0))
+        self.n_rows, self.n_columns = dataMatrix.shape
+        self.TopK = min(int(topK), self.n_columns)
+        self.similarity = similarity
+        # the reference sums the squares behind the norms in float32, in an order that follows the sparse format it is handed
+        # (include/mi355rec.h, norm_sum_order): CSC input and pearson (whose pre-pass converts to CSC) -> NumPy's pairwise reduceat
+        # order, everything else (CSR, the adjusted-cosine pre-pass, ndarray / COO input) -> one square after the other in row order
+        norm_sum_order = self._norm_sum_order(similarity, sps.isspmatrix_csc(dataMatrix))
+        rw = self._row_weights(row_weights)
+        csr = check_matrix(dataMatrix, "csr", dtype=np.float32)
+        if not csr.has_sorted_indices:
+            csr = csr.sorted_indices()
+        indptr, indices, data = N.as_i32(csr.indptr), N.as_i32(csr.indices), N.as_f32(csr.data)
+        cfg = self._config(shrink, normalize, asymmetric_alpha, tversky_alpha, tversky_beta, unit_column_side, normalize_avg_row,
+                           similarity_from_distance_mode, feature_weighting, weighting_documents, K1, B, norm_sum_order)
+        self._weighted_structure = (csr.indptr, csr.indices, csr.shape) if feature_weighting != "none" else None
+        if resident is not None:
+            if not resident.matches(csr):
+                raise ValueError("Compute_Similarity_MI355X: `resident` does not hold this dataMatrix (shape, nnz or contents differ)")
+            self._create(C.byref(cfg), self.n_rows, self.n_columns, resident.indptr.ptr, resident.indices.ptr, resident.data.ptr, N.ptr(rw),
+                         entry="create_resident")
+        else:
+            self._create(C.byref(cfg), self.n_rows, self.n_columns, N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(rw))
+
+    @classmethod
+    def from_resident(cls, resident, norm_sum_order, topK=100, shrink=0, normalize=True, asymmetric_alpha=0.5, tversky_alpha=1.0,
+                      tversky_beta=1.0, similarity="cosine", row_weights=None, unit_column_side=False, feature_weighting="none",
+                      weighting_documents="columns", K1=1.2, B=0.75):
+        """The same build started from a matrix that exists in device memory ONLY: `resident` is a `_native.ResidentStack`, there is no host copy to compare it with and none is made.  norm_sum_order: the sparse format the reference
+        would be handed for this matrix -- 0: CSR, 1: CSC (`ICM_train.T` of a CSR ICM is CSC) -- which decides the order its float32
+        sums behind the norms take (include/mi355rec.h); pearson and adjusted cosine convert the matrix themselves and override it,
+        as in the constructor.  TF-IDF's non-negativity is judged by `resident.values_nonnegative()` (host copies of the blocks and
+        the signs of their scales); non-finite values are found by the library's own pass.  `weighted_matrix()` reads its structure
+        back from the device.  Not for similarity="euclidean" (that front-end squares the values on the host)."""
+        if similarity == "euclidean":
+            raise ValueError("Compute_Similarity_MI355X.from_resident: the Euclidean front-end builds from a host matrix")
+        if norm_sum_order not in (0, 1):
+            raise ValueError("Compute_Similarity_MI355X.from_resident: norm_sum_order must be 0 (CSR order) or 1 (CSC order)")
+        self = cls.__new__(cls)
+        self._check_arguments(similarity, feature_weighting, weighting_documents, K1, B)
+        if feature_weighting == "TF-IDF":
+            assert resident.values_nonnegative(), "TF_IDF: Data matrix contains negative values, computing the square root is not possible."
+        self.n_rows, self.n_columns = resident.shape
+        self.TopK = min(int(topK), self.n_columns)
+        self.similarity = similarity
+        rw = self._row_weights(row_weights)
+        cfg = self._config(shrink, normalize, asymmetric_alpha, tversky_alpha, tversky_beta, unit_column_side, False, "lin",
+                           feature_weighting, weighting_documents, K1, B, self._norm_sum_order(similarity, norm_sum_order == 1))
+        self._weighted_structure = resident if feature_weighting != "none" else None
+        self._create(C.byref(cfg), self.n_rows, self.n_columns, resident.indptr.ptr, resident.indices.ptr, resident.data.ptr, N.ptr(rw),
+                     entry="create_resident")
+        return self
+
+    def _check_arguments(self, similarity, feature_weighting, weighting_documents, K1, B):
         if similarity not in self.SIMILARITY_VALUES and similarity != "euclidean":
             raise ValueError("Cosine_Similarity: value for parameter 'mode' not recognized."
                              " Allowed values are: 'cosine', 'pearson', 'adjusted', 'asymmetric', 'jaccard', 'tanimoto',"
@@ -54,47 +111,38 @@ class Compute_Similarity_MI355X(N.Handle):
         if feature_weighting == "BM25":
             assert 0 < B < 1, "okapi_BM_25: B must be in (0,1)"
             assert K1 > 0, "okapi_BM_25: K1 must be > 0"
-        if feature_weighting == "TF-IDF":
-            assert np.all(dataMatrix.data >= 0.0), \
-                "TF_IDF: Data matrix contains {} negative values, computing the square root is not possible.".format(np.sum(dataMatrix.data < 0.0))
-        self.n_rows, self.n_columns = dataMatrix.shape
-        self.TopK = min(int(topK), self.n_columns)
-        self.similarity = similarity
+        assert weighting_documents in ("columns", "rows")
+
+    @staticmethod
+    def _norm_sum_order(similarity, handed_csc):
+        return 1 if (similarity == "pearson" or (handed_csc and similarity != "adjusted")) else 0
+
+    def _row_weights(self, row_weights):
         if row_weights is not None and self.n_rows != len(row_weights):
             raise ValueError("Cosine_Similarity: provided row_weights and dataMatrix have different number of rows."
                              "Row_weights has {} rows, dataMatrix has {}.".format(len(row_weights), self.n_rows))
-        # the reference sums the squares behind the norms in float32, in an order that follows the sparse format it is handed
-        # (include/mi355rec.h, norm_sum_order): CSC input and pearson (whose pre-pass converts to CSC) -> NumPy's pairwise reduceat
-        # order, everything else (CSR, the adjusted-cosine pre-pass, ndarray / COO input) -> one square after the other in row order
-        norm_sum_order = 1 if (similarity == "pearson" or (sps.isspmatrix_csc(dataMatrix) and similarity != "adjusted")) else 0
-        csr = check_matrix(dataMatrix, "csr", dtype=np.float32)
-        if not csr.has_sorted_indices:
-            csr = csr.sorted_indices()
-        indptr, indices, data = N.as_i32(csr.indptr), N.as_i32(csr.indices), N.as_f32(csr.data)
-        rw = None if row_weights is None else N.as_f32(row_weights)
-        cfg = N.SimConfig(self.TopK, int(shrink), int(bool(normalize)), N.SIMILARITY_CODES[similarity],
-                          float(asymmetric_alpha), float(tversky_alpha), float(tversky_beta), int(bool(unit_column_side)),
-                          int(bool(normalize_avg_row)), N.EUCLIDEAN_MODE_CODES.get(similarity_from_distance_mode, -1),
-                          N.FEATURE_WEIGHTING_CODES[feature_weighting], int(weighting_documents == "rows"), float(K1), float(B),
-                          norm_sum_order, 0)
-        assert weighting_documents in ("columns", "rows")
-        self._weighted_structure = (csr.indptr, csr.indices, csr.shape) if feature_weighting != "none" else None
-        if resident is not None:
-            if not resident.matches(csr):
-                raise ValueError("Compute_Similarity_MI355X: `resident` does not hold this dataMatrix (shape, nnz or contents differ)")
-            self._create(C.byref(cfg), self.n_rows, self.n_columns, resident.indptr.ptr, resident.indices.ptr, resident.data.ptr, N.ptr(rw),
-                         entry="create_resident")
-        else:
-            self._create(C.byref(cfg), self.n_rows, self.n_columns, N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(rw))
+        return None if row_weights is None else N.as_f32(row_weights)
+
+    def _config(self, shrink, normalize, asymmetric_alpha, tversky_alpha, tversky_beta, unit_column_side, normalize_avg_row,
+                similarity_from_distance_mode, feature_weighting, weighting_documents, K1, B, norm_sum_order):
+        return N.SimConfig(self.TopK, int(shrink), int(bool(normalize)), N.SIMILARITY_CODES[self.similarity],
+                           float(asymmetric_alpha), float(tversky_alpha), float(tversky_beta), int(bool(unit_column_side)),
+                           int(bool(normalize_avg_row)), N.EUCLIDEAN_MODE_CODES.get(similarity_from_distance_mode, -1),
+                           N.FEATURE_WEIGHTING_CODES[feature_weighting], int(weighting_documents == "rows"), float(K1), float(B),
+                           norm_sum_order, 0)
 
     def weighted_matrix(self):
         """The BM25 / TF-IDF re-weighted dataMatrix (csr, float32), computed on the device by the constructor."""
         if self._weighted_structure is None:
             raise ValueError("Compute_Similarity_MI355X was created with feature_weighting='none'")
-        indptr, indices, shape = self._weighted_structure
+        if isinstance(self._weighted_structure, tuple):
+            indptr, indices, shape = self._weighted_structure
+            indptr, indices = indptr.copy(), indices.copy()
+        else:           # (from_resident: the structure exists on the device only)
+            (indptr, indices), shape = self._weighted_structure.structure(), self._weighted_structure.shape
         data = np.empty(len(indices), np.float32)
         self._call("get_weighted_values", N.ptr(data))
-        return sps.csr_matrix((data, indices.copy(), indptr.copy()), shape=shape)
+        return sps.csr_matrix((data, indices, indptr), shape=shape)
 
     def _range(self, start_col, end_col):
         # same acceptance rule as Compute_Similarity_Cython.pyx:447-451
@@ -232,16 +280,9 @@ class Compute_Similarity:
                 np.sum(np.logical_not(np.isfinite(dataMatrix.data)))))
         if similarity == "euclidean" and not np.all(np.isfinite(dataMatrix.data)):        # (that front-end squares the values first)
             raise non_finite()
-        assert similarity == "euclidean" or not (dataMatrix.shape[0] == 1 and dataMatrix.nnz == dataMatrix.shape[1]), \
-            "Compute_Similarity: data has only 1 feature (shape: {}) with dense values," \
-            " vector and set based similarities are not defined on 1-dimensional dense data," \
-            " use Euclidean similarity instead.".format(dataMatrix.shape)
+        self.check_request(dataMatrix.shape, dataMatrix.nnz, similarity, use_implementation)
         if similarity is not None:
             args["similarity"] = similarity
-        if use_implementation not in ("density", "cython", "mi355x"):
-            if use_implementation == "python":
-                raise NotImplementedError("Compute_Similarity: the NumPy implementation is not provided here")
-            raise ValueError("Compute_Similarity: value for argument 'use_implementation' not recognized")
         if isinstance(dataMatrix, np.ndarray):
             dataMatrix = sps.csr_matrix(dataMatrix)
         if similarity == "euclidean":
@@ -255,6 +296,19 @@ class Compute_Similarity:
                 if "non finite" in str(exc):
                     raise non_finite() from None
                 raise
+
+    @staticmethod
+    def check_request(shape, nnz, similarity, use_implementation):
+        """What the dispatcher refuses whatever the matrix holds: one dense feature row, and implementations that are not the device's
+        (also asked by the builds that start from device memory and never come through this class)."""
+        assert similarity == "euclidean" or not (shape[0] == 1 and nnz == shape[1]), \
+            "Compute_Similarity: data has only 1 feature (shape: {}) with dense values," \
+            " vector and set based similarities are not defined on 1-dimensional dense data," \
+            " use Euclidean similarity instead.".format(shape)
+        if use_implementation not in ("density", "cython", "mi355x"):
+            if use_implementation == "python":
+                raise NotImplementedError("Compute_Similarity: the NumPy implementation is not provided here")
+            raise ValueError("Compute_Similarity: value for argument 'use_implementation' not recognized")
 
     def compute_similarity(self, **args):
         return self.compute_similarity_object.compute_similarity(**args)
