@@ -611,6 +611,54 @@ int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Non-personalized models: one vector of item scores for every user  (Base/NonPersonalizedRecommender.py:30-43,119-132
+ * _compute_item_score of TopPop / GlobalEffects repeats it per user; Base/BaseRecommender.py:131-222 recommend filters and ranks)
+ * ---------------------------------------------------------------------------------------------------- */
+
+typedef struct mi355rec_itemscorer *mi355rec_itemscorer_t;
+
+/* item_scores: float32[n_items]; the "seen" CSR is URM_train (rows sorted or not, repeats allowed).  The vector is sorted once, here
+ * and in update: a user's list is the head of that order without the user's seen items -- work of cutoff + profile length per user. */
+int mi355rec_itemscorer_create(mi355rec_itemscorer_t *out, int32_t n_users, int32_t n_items, const float *item_scores,
+                               const int32_t *seen_indptr, const int32_t *seen_indices);
+/* The same with the seen CSR in device memory (a resident URM's indptr / indices, seen_nnz cells): copied device to device. */
+int mi355rec_itemscorer_create_resident(mi355rec_itemscorer_t *out, int32_t n_users, int32_t n_items, const float *item_scores,
+                                        const int32_t *d_seen_indptr, const int32_t *d_seen_indices, int64_t seen_nnz);
+/* A new vector of the same length. */
+int mi355rec_itemscorer_update(mi355rec_itemscorer_t h, const float *item_scores);
+/* As mi355rec_scorer_recommend: ranked[(row) * cutoff ...] = the cutoff best items that are finite in the vector, allowed by the
+ * mask (nullable) and -- remove_seen -- not seen by the user; score descending, ties towards the lower item id, -1 padded.  A
+ * non-finite entry of the vector is never listed.  scores (nullable, n x n_items): the vector in every row, -inf where a filter
+ * applies. */
+int mi355rec_itemscorer_recommend(mi355rec_itemscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
+                                  const uint8_t *item_allowed, int32_t *ranked, float *scores);
+/* As mi355rec_scorer_recommend_candidates: the vector is gathered at the candidates of each row. */
+int mi355rec_itemscorer_recommend_candidates(mi355rec_itemscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
+                                             const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
+                                             const uint8_t *item_allowed, int32_t *ranked);
+/* W: positions of the order one pass of the ranking kernel covers -- 2048 with a wavefront per user, 8192 with a 256-lane
+ * workgroup per user.  set_window_bits chooses between the two kernel shapes (any other value is MI355REC_E_INVALID). */
+int mi355rec_itemscorer_window_bits(mi355rec_itemscorer_t h, int32_t *bits);
+int mi355rec_itemscorer_set_window_bits(mi355rec_itemscorer_t h, int32_t bits);
+/* kernel_ms = call_ms = everything the last recommend / recommend_candidates put on the stream; n_units = n. */
+int mi355rec_itemscorer_get_stats(mi355rec_itemscorer_t h, mi355rec_stats *stats);
+void mi355rec_itemscorer_destroy(mi355rec_itemscorer_t h);
+
+/* TopPop.fit (Base/NonPersonalizedRecommender.py:23-27): item_counts[n_items] = stored cells per column of the CSR matrix, without
+ * a CSC copy.  _resident: the arrays are device pointers (nnz stored cells); item_counts is host memory in both. */
+int mi355rec_urm_item_counts(int32_t n_users, int32_t n_items, const int32_t *indptr, const int32_t *indices, int32_t *item_counts);
+int mi355rec_urm_item_counts_resident(int32_t n_users, int32_t n_items, int32_t nnz, const int32_t *d_indptr, const int32_t *d_indices,
+                                      int32_t *item_counts);
+/* GlobalEffects.fit (:71-116) on the CSR matrix: mu = float32(sum x / nnz); d = float32(x - mu); item_bias[c] = sum over column c of
+ * d / (col_nnz + lambda_item); d' = float32(double(d) - item_bias[col]); user_bias[r] = sum over row r of d' / (row_nnz +
+ * lambda_user).  Sums are float64 in a fixed order (the same bits on every run); the outputs are host memory. */
+int mi355rec_urm_global_effects(int32_t n_users, int32_t n_items, const int32_t *indptr, const int32_t *indices, const float *data,
+                                double lambda_user, double lambda_item, float *mu, double *item_bias, double *user_bias);
+int mi355rec_urm_global_effects_resident(int32_t n_users, int32_t n_items, int32_t nnz, const int32_t *d_indptr, const int32_t *d_indices,
+                                         const float *d_data, double lambda_user, double lambda_item, float *mu, double *item_bias,
+                                         double *user_bias);
+
+/* ------------------------------------------------------------------------------------------------------
  * Holdout evaluation  (Base/Evaluation/Evaluator.py:225-275 evaluateRecommender, :294-374 _compute_metrics_on_recommendation_list,
  * :404-450 EvaluatorHoldout._run_evaluation_on_selected_users; the metric functions of Base/Evaluation/metrics.py)
  * ---------------------------------------------------------------------------------------------------- */
@@ -643,6 +691,8 @@ int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_
                              const uint8_t *item_allowed);
 int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                const uint8_t *item_allowed);
+int mi355rec_eval_add_itemscorer(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                 const uint8_t *item_allowed);
 /* Negative-sample evaluation (Evaluator.py:455-539 EvaluatorNegativeItemSample): the candidate rows of ALL n_users users as CSR
  * (indptr[n_users + 1]; item ids strictly ascending inside a row, else MI355REC_E_INVALID), uploaded once per evaluator.
  * MI355REC_E_UNSUPPORTED when a row holds more than 4096 items or the lists are more than 4096 wide. */
@@ -653,6 +703,8 @@ int mi355rec_eval_add_scorer_candidates(mi355rec_eval_t h, mi355rec_scorer_t sco
                                         const uint8_t *item_allowed);
 int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                           const uint8_t *item_allowed);
+int mi355rec_eval_add_itemscorer_candidates(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                            const uint8_t *item_allowed);
 /* sums[c * MI355REC_EVAL_VALUES + v]: value v summed over the evaluated users in a fixed order (the last one is the covered-user
  * count); item_counts[c * n_items + i]: times item i was recommended within cutoff c (the recommended_counter of
  * metrics.py:284-286, 762-769). */

@@ -199,14 +199,29 @@ SIGNATURES = {
     "mi355rec_spscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mi355rec_spscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_spscorer_destroy": (None, [_vp]),
+    "mi355rec_itemscorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_itemscorer_create_resident": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _i64]),
+    "mi355rec_itemscorer_update": (C.c_int, [_vp, _vp]),
+    "mi355rec_itemscorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_itemscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "mi355rec_itemscorer_window_bits": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "mi355rec_itemscorer_set_window_bits": (C.c_int, [_vp, _i32]),
+    "mi355rec_itemscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
+    "mi355rec_itemscorer_destroy": (None, [_vp]),
+    "mi355rec_urm_item_counts": (C.c_int, [_i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_urm_item_counts_resident": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_urm_global_effects": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _f64, _f64, C.POINTER(_f32), _vp, _vp]),
+    "mi355rec_urm_global_effects_resident": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, C.POINTER(_f32), _vp, _vp]),
     "mi355rec_eval_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32]),
     "mi355rec_eval_begin": (C.c_int, [_vp, _vp, _vp, _vp, _i32]),
     "mi355rec_eval_add_lists": (C.c_int, [_vp, _i32, _i32, _vp]),
     "mi355rec_eval_add_scorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_spscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_itemscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_set_candidates": (C.c_int, [_vp, _vp, _vp]),
     "mi355rec_eval_add_scorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_spscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_itemscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_finish": (C.c_int, [_vp, _vp, _vp]),
     "mi355rec_eval_get_per_user": (C.c_int, [_vp, _vp]),
     "mi355rec_eval_destroy": (None, [_vp]),

@@ -16,57 +16,12 @@
 #include "common.h"
 #include "score.h"
 #include "topk.cuh"
+#include "cand.cuh"
 
 #include <algorithm>
 
 namespace mi355rec {
 namespace {
-
-static_assert(CAND_MAX == AUX_WORDS / 2, "a candidate row is one block_rank_emit over the 32 KiB candidate buffer");
-constexpr int CAND_THREADS = 256;
-
-struct CandParams {
-    int cutoff, remove_seen, by_user;
-    const int *users, *seen_ptr, *seen_idx;
-    const int *cand_ptr, *cand_idx;
-    const unsigned char *allowed;   // nullable, as RankParams::allowed
-    int *ranked;
-};
-
-__device__ __forceinline__ uint64_t cand_entry(float v, int pos) {
-    if (!(v > -INFINITY)) v = -INFINITY;                            // (NaN is not admissible either, as in the full-row ranking)
-    return ((uint64_t)float_key(v) << 32) | (uint32_t)(~(uint32_t)pos);
-}
-
-// cand[0 .. ncand): the candidates' entries, mask filter applied, written by the caller (no barrier needed behind the writes);
-// *nfinite and sc.out_count are 0.  Seen items -> -inf, then the ranking of the admissible ones, -1 padded.
-template <int THREADS>
-__device__ __forceinline__ void cand_filter_rank(const CandParams &p, int u, const int *items, int ncand, uint64_t *cand, SelectScratch &sc,
-                                                 uint32_t *nfinite, int *out) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    __syncthreads();
-    if (p.remove_seen) {            // _remove_seen_on_scores (BaseRecommender.py:110-117); the seen row need not be sorted, `items` is
-        for (int q = p.seen_ptr[u] + tid; q < p.seen_ptr[u + 1]; q += THREADS) {
-            const int s = p.seen_idx[q];
-            int lo = 0, hi = ncand;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (items[mid] < s) lo = mid + 1; else hi = mid;
-            }
-            if (lo < ncand && items[lo] == s) cand[lo] = cand_entry(-INFINITY, lo);
-        }
-        __syncthreads();
-    }
-    uint32_t nfin = 0;
-    for (int i = tid; i < ncand; i += THREADS) nfin += (uint32_t)(cand[i] >> 32) > float_key(-INFINITY);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nfin += __shfl_down(nfin, off);
-    if (lane == 0 && nfin) atomicAdd(nfinite, nfin);
-    __syncthreads();
-    // the -inf entries hold the lowest keys: they rank behind every admissible candidate and K stops in front of them
-    const uint32_t K = min((uint32_t)p.cutoff, *nfinite);
-    block_rank_emit<THREADS>(cand, ncand, p.cutoff, K, 0u, sc, out, nullptr, 0, items);
-}
 
 struct CandScoreParams {
     CandParams c;
@@ -198,23 +153,6 @@ __global__ __launch_bounds__(THREADS) void cand_gather_rank_kernel(const CandPar
     cand_filter_rank<THREADS>(c, u, items, ncand, cand, sc, &s_nfinite, c.ranked + (size_t)b * c.cutoff);
 }
 
-// entries of the LDS candidate buffer: the row, or the power of two block_rank_emit's bitonic branch pads a row above 1024 to
-int cand_buffer_entries(int longest) {
-    if (longest <= 1024) return std::max(2, (longest + 1) & ~1);
-    int P = 2048;
-    while (P < longest) P <<= 1;
-    return P;
-}
-
-CandParams cand_params(ScorerHandle *h, const int *users, int cutoff, int remove_seen, const unsigned char *allowed, const CandidateRows &rows) {
-    CandParams c{};
-    c.cutoff = cutoff; c.remove_seen = remove_seen; c.by_user = rows.by_user;
-    c.users = users; c.seen_ptr = h->seen_ptr.ptr; c.seen_idx = h->seen_idx.ptr;
-    c.cand_ptr = rows.ptr; c.cand_idx = rows.idx;
-    c.allowed = allowed; c.ranked = h->ranked.ptr;
-    return c;
-}
-
 }  // namespace
 
 void check_candidate_cutoff(int cutoff) {
@@ -236,14 +174,6 @@ int check_candidate_rows(const int32_t *indptr, const int32_t *indices, int n_ro
     }
     if (longest > CAND_MAX) fail(MI355REC_E_UNSUPPORTED, "a candidate row of %d items: at most %d", longest, CAND_MAX);
     return longest;
-}
-
-// (buffers only grow after the stream has drained, as in scorer_enqueue)
-static void grow_ranked(ScorerHandle *h, size_t cells) {
-    if (h->ranked.count < cells) {
-        MI_HIP(hipStreamSynchronize(h->stream));
-        h->ranked.alloc(cells);
-    }
 }
 
 Ranking scorer_enqueue_candidates(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
@@ -305,43 +235,6 @@ Ranking spscorer_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int
 }  // namespace mi355rec
 
 using namespace mi355rec;
-
-namespace {
-// The body of mi355rec_scorer_recommend_candidates and mi355rec_spscorer_recommend_candidates: row r of the candidate CSR belongs to
-// user_ids[r]; user ids, the rows and the item mask go up, `enqueue` ranks, the lists come down.
-template <class H, class Enqueue, class BadUser>
-void recommend_candidates(H *h, const int32_t *user_ids, int n, const int32_t *cand_indptr, const int32_t *cand_indices, int cutoff,
-                          int remove_seen, const uint8_t *item_allowed, int32_t *ranked, Enqueue enqueue, BadUser bad_user) {
-    MI_REQUIRE(h && user_ids && cand_indptr && ranked, "NULL argument");
-    MI_REQUIRE(n > 0, "empty user batch");
-    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-    for (int i = 0; i < n; ++i)
-        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) bad_user(user_ids[i]);
-    const int longest = check_candidate_rows(cand_indptr, cand_indices, n, h->n_items);
-    check_candidate_cutoff(cutoff);     // (before anything is uploaded; the enqueue functions check for every caller)
-    ensure_device();
-    hipStream_t s = h->stream;
-    const size_t nnz = (size_t)cand_indptr[n];
-    if (h->users.count < (size_t)n || h->cand_ptr.count < (size_t)n + 1 || h->cand_idx.count < std::max<size_t>(nnz, 1)) {
-        MI_HIP(hipStreamSynchronize(s));
-        if (h->users.count < (size_t)n) h->users.alloc(n);
-        if (h->cand_ptr.count < (size_t)n + 1) h->cand_ptr.alloc((size_t)n + 1);
-        if (h->cand_idx.count < std::max<size_t>(nnz, 1)) h->cand_idx.alloc(std::max<size_t>(nnz, 1));
-    }
-    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-    MI_HIP(hipMemcpyAsync(h->cand_ptr.ptr, cand_indptr, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
-    if (nnz) MI_HIP(hipMemcpyAsync(h->cand_idx.ptr, cand_indices, sizeof(int) * nnz, hipMemcpyHostToDevice, s));
-    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-    enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr,
-            CandidateRows{h->cand_ptr.ptr, h->cand_idx.ptr, false, longest});
-    h->ranked.download(ranked, (size_t)n * cutoff, s);
-    MI_HIP(hipStreamSynchronize(s));
-    h->stats = mi355rec_stats{};
-    h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms();      // the candidate kernel(s): there is no GEMM to tell apart
-    h->stats.n_launches = h->stats.n_timed = 1;
-    h->stats.n_units = n;
-}
-}  // namespace
 
 extern "C" int mi355rec_scorer_recommend_candidates(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                                     const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,

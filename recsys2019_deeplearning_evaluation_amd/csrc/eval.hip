@@ -15,6 +15,7 @@
 // by mi355rec_eval_set_candidates); the metric kernel and finish are the same.
 #include "common.h"
 #include "score.h"
+#include "itemscore.h"
 #include "wave.cuh"
 
 #include <algorithm>
@@ -407,6 +408,11 @@ extern "C" int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t
     return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue); });
 }
 
+extern "C" int mi355rec_eval_add_itemscorer(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                            const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue); });
+}
+
 // Negative-sample evaluation (Evaluator.py:455-539, EvaluatorNegativeItemSample): every user ranks the candidates of its row only.
 extern "C" int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *indptr, const int32_t *indices) {
     return guarded([&] {
@@ -447,6 +453,11 @@ extern "C" int mi355rec_eval_add_scorer_candidates(mi355rec_eval_t h, mi355rec_s
 extern "C" int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n,
                                                      int32_t remove_seen, const uint8_t *item_allowed) {
     return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue_candidates); });
+}
+
+extern "C" int mi355rec_eval_add_itemscorer_candidates(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n,
+                                                       int32_t remove_seen, const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue_candidates); });
 }
 
 extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts) {

@@ -4,7 +4,7 @@ per-user metric loop (:294-374, Base/Evaluation/metrics.py) run by a HIP kernel 
 `EvaluatorHoldout_MI355X` takes the reference's constructor arguments and returns the reference's `(results_dict, results_string)`,
 so early stopping (`Incremental_Training_Early_Stopping._train_with_early_stopping`) and the reference's search classes take it as
 their `evaluator_object` unchanged.  Two paths:
-  fused  recommenders with a device scorer (GpuScoringMixin / GpuSimilarityScoringMixin): each block of users is scored,
+  fused  recommenders with a device scorer (GpuScoringMixin / GpuSimilarityScoringMixin / GpuItemScoreMixin): each block of users is scored,
          ranked and evaluated on the device; neither scores nor lists reach the host.
   lists  any other recommender: recommend(..., return_scores=False) on the host, the lists uploaded, the same metric kernel.
 `EvaluatorNegativeItemSample_MI355X` is the reference's EvaluatorNegativeItemSample (Evaluator.py:455-539) on the same two paths: every
@@ -21,7 +21,7 @@ import numpy as np
 import scipy.sparse as sps
 
 from . import _native as N
-from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin, allowed_items
+from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin, allowed_items
 
 # EvaluatorMetrics order (Evaluator.py:20-40), without DIVERSITY_SIMILARITY
 METRICS = ["ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", "MRR", "NDCG", "F1", "HIT_RATE", "ARHR", "NOVELTY",
@@ -120,6 +120,7 @@ class EvaluatorHoldout_MI355X(N.Handle):
     _PREFIX = "mi355rec_eval"
 
     EVALUATOR_NAME = "EvaluatorHoldout_MI355X"
+    FUSED_BLOCK = 16384             # users per launch of the scorers that keep no n x n_items score buffer (candidate rows, item vector)
 
     def __init__(self, URM_test_list, cutoff_list, min_ratings_per_user=1, exclude_seen=True, diversity_object=None,
                  ignore_items=None, ignore_users=None, verbose=True):
@@ -219,6 +220,9 @@ class EvaluatorHoldout_MI355X(N.Handle):
             self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
         elif isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
+        elif isinstance(rec, GpuItemScoreMixin):       # (no n x n_items score buffer bounds a launch: fewer, larger blocks)
+            self._run_fused(rec._get_item_scorer(), "add_itemscorer", rec,
+                            int(block_size) if block_size else min(self.FUSED_BLOCK, len(self.users_to_evaluate)))
         else:
             self._run_lists(rec, block)
 
@@ -289,7 +293,6 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
     send every recommender through recommend()."""
 
     EVALUATOR_NAME = "EvaluatorNegativeItemSample_MI355X"
-    FUSED_BLOCK = 16384             # users per launch of the factor scorer's candidate kernel (there is no n x n_items buffer to bound)
 
     def __init__(self, URM_test_list, URM_test_negative, cutoff_list, min_ratings_per_user=1, exclude_seen=True, diversity_object=None,
                  ignore_items=None, ignore_users=None, verbose=True):
@@ -318,6 +321,8 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
             self._run_fused(rec._get_scorer(), "add_scorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
         elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer_candidates", rec, int(block_size) if block_size else self._block_size())
+        elif self.candidates_on_device and isinstance(rec, GpuItemScoreMixin):
+            self._run_fused(rec._get_item_scorer(), "add_itemscorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
         else:
             self._run_lists(rec, int(block_size) if block_size else self._block_size())
 

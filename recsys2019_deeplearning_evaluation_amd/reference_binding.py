@@ -18,6 +18,8 @@ the package works where the reference tree is not importable.  Inside the refere
 `bind(..., BaseItemCBFRecommender=..., BaseUserCBFRecommender=...)` (`Base.BaseCBFRecommender`) adds the content-based and hybrid KNN
 recommenders and ItemKNNCustomSimilarityRecommender to the namespace.
 
+`bind(..., BaseRecommender=...)` (`Base.BaseRecommender`) adds TopPop, GlobalEffects and Random.
+
 `device_scoring=False` leaves `recommend()` to the reference's own host implementation (Base/BaseRecommender.py:131).
 """
 from types import SimpleNamespace
@@ -30,17 +32,20 @@ from .knn_cbf import (_ItemKNNCBFLogic, _ItemKNNCFCBFHybridLogic, _ItemKNNCustom
                       _UserKNNCFCBFHybridLogic)
 from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
 from .nmf import _NMFLogic
+from .non_personalized import _GlobalEffectsLogic, _RandomLogic, _TopPopLogic
 from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
-from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin
+from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin
 from .slim_bpr import _SLIMLogic
 from .slim_elasticnet import _SLIMElasticNetLogic
 
 
 def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender, BaseUserSimilarityMatrixRecommender,
-         Incremental_Training_Early_Stopping, device_scoring=True, BaseItemCBFRecommender=None, BaseUserCBFRecommender=None):
+         Incremental_Training_Early_Stopping, device_scoring=True, BaseItemCBFRecommender=None, BaseUserCBFRecommender=None,
+         BaseRecommender=None):
     """Returns a namespace with every recommender of this package rebuilt on the given (reference) base classes.  The content-based
     and hybrid KNN recommenders need `Base.BaseCBFRecommender`'s two classes as well: they are rebuilt when BaseItemCBFRecommender and
-    BaseUserCBFRecommender are given (ItemKNNCustomSimilarityRecommender with the item pair)."""
+    BaseUserCBFRecommender are given (ItemKNNCustomSimilarityRecommender with the item pair).  The non-personalized recommenders
+    (TopPop, GlobalEffects, Random) derive from `Base.BaseRecommender` itself: they are rebuilt when BaseRecommender is given."""
     mf_score = (GpuScoringMixin,) if device_scoring else ()
     sim_score = (GpuSimilarityScoringMixin,) if device_scoring else ()
     mf = mf_score + (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
@@ -69,4 +74,9 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
         user_cbf = sim_score + (BaseUserCBFRecommender, BaseUserSimilarityMatrixRecommender)
         table["UserKNNCBFRecommender"] = (_UserKNNCBFLogic,) + user_cbf
         table["UserKNN_CFCBF_Hybrid_Recommender"] = (_UserKNNCFCBFHybridLogic,) + user_cbf
+    if BaseRecommender is not None:
+        item_score = (GpuItemScoreMixin,) if device_scoring else ()
+        table["TopPop"] = (_TopPopLogic,) + item_score + (BaseRecommender,)
+        table["GlobalEffects"] = (_GlobalEffectsLogic,) + item_score + (BaseRecommender,)
+        table["Random"] = (_RandomLogic, BaseRecommender)                  # (scored on the host: see _RandomLogic)
     return SimpleNamespace(**{name: type(name, bases, {"__doc__": bases[0].__doc__}) for name, bases in table.items()})

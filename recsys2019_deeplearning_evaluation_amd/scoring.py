@@ -227,3 +227,74 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
 
     def _scorer_for(self, users):
         return self._get_sparse_scorer()
+
+
+class MI355XItemScorer(_Scorer):
+    """One vector of item scores for every user (the reference's non-personalized models, Base/NonPersonalizedRecommender.py:30-43,
+    119-132), filtered and ranked on the device like MI355XScorer.  The vector is sorted once per model; a user's list is the head of
+    that order without the user's seen items -- work of cutoff + profile length per user instead of n_items.  A non-finite entry of
+    the vector is never listed.  `URM_seen` is a host matrix or a `ResidentURM` (its structure is then copied device to device)."""
+    _PREFIX = "mi355rec_itemscorer"
+
+    def __init__(self, item_scores, URM_seen):
+        vec = N.as_f32(np.asarray(item_scores).ravel())
+        self.n_users, self.n_items = URM_seen.shape
+        assert len(vec) == self.n_items, "item_scores has {} entries for {} items".format(len(vec), self.n_items)
+        if isinstance(URM_seen, N.ResidentURM):
+            self._create(self.n_users, self.n_items, N.ptr(vec), URM_seen.indptr.ptr, URM_seen.indices.ptr, URM_seen.nnz,
+                         entry="create_resident")
+        else:
+            seen = URM_seen.tocsr()
+            indptr, indices = N.as_i32(seen.indptr), N.as_i32(seen.indices)
+            self._create(self.n_users, self.n_items, N.ptr(vec), N.ptr(indptr), N.ptr(indices))
+
+    def update(self, item_scores):
+        vec = N.as_f32(np.asarray(item_scores).ravel())
+        assert len(vec) == self.n_items
+        self._call("update", N.ptr(vec))
+
+    def window_bits(self):
+        """W: positions of the sorted order one pass of the ranking kernel covers (2048: a wavefront per user, 8192: a workgroup)."""
+        bits = C.c_int32(0)
+        self._call("window_bits", C.byref(bits))
+        return int(bits.value)
+
+    def set_window_bits(self, bits):
+        self._call("set_window_bits", int(bits))
+
+
+class GpuItemScoreMixin(_ScoringMixin):
+    """recommend() for recommenders whose scores are one vector shared by all users, served by MI355XItemScorer.  The vector is
+    `_item_score_vector()`; the cache follows the rules of the other two mixins: strong references, identity plus `_fingerprint` of
+    the vector (a new vector of the same length is an update), a new scorer when URM_train is replaced.  `_resident_urm`, when the
+    recommender has one that holds URM_train, also serves as the scorer's seen CSR.  A model restored by load_model is scored
+    without a fit."""
+    _item_scorer = None
+    _item_scorer_src = None
+    _resident_urm = None
+    _SCORER_ATTRS = ("_item_scorer", "_item_scorer_src")
+
+    def _item_score_vector(self):
+        raise NotImplementedError("{}: _item_score_vector".format(type(self).__name__))
+
+    def _get_item_scorer(self):
+        vector = self._item_score_vector()
+        print_now = _fingerprint(vector)
+        old = self._item_scorer_src
+        if self._item_scorer is None or old["urm"] is not self.URM_train:
+            if self._item_scorer is not None:
+                self._item_scorer.close()
+            resident = self._resident_urm
+            seen = resident if resident is not None and resident.matches(self.URM_train) else self.URM_train
+            self._item_scorer = MI355XItemScorer(vector, seen)
+        elif old["vector"] is not vector or old["print"] != print_now:
+            self._item_scorer.update(vector)
+        self._item_scorer_src = {"vector": vector, "print": print_now, "urm": self.URM_train}
+        return self._item_scorer
+
+    def _scorer_for(self, users):
+        scorer = self._get_item_scorer()
+        assert scorer.n_users > np.max(users), \
+            "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
+                self.RECOMMENDER_NAME, scorer.n_users, np.max(users))
+        return scorer
