@@ -584,3 +584,92 @@ def oracle_ials_epoch(C_csr, C_csc, U, V, reg):
         if limit is not None:
             limit.restore_original_limits()
     return U, V
+
+
+# --------------------------------------------------------------------------------------------------
+#                                   P3alpha / RP3beta (random walk)
+# --------------------------------------------------------------------------------------------------
+
+def oracle_walk_inputs(URM, alpha, beta=None, min_rating=0, implicit=False):
+    """The two factors of the walk, float64: (B, M, item_count) with
+         B[u, i] = 1 for every STORED entry of the URM (after the min_rating filter),
+         M[u, j] = (r_uj / sum_j |r_uj|)^alpha  (* item_count[j]^-beta when beta is not None),
+         item_count[i] = stored entries of column i -- the degree of the boolean transpose.
+    min_rating > 0 zeroes the ratings below it and drops them; `implicit` sets what is left to 1 and -- like the reference -- acts
+    only inside that branch: implicit=True with min_rating=0 changes nothing.  The degree counts stored entries, so an explicit
+    zero that survives (min_rating == 0) counts as an interaction whose M value is 0."""
+    X = sps.csr_matrix(URM, dtype=np.float64, copy=True)
+    if min_rating > 0:
+        X.data[X.data < min_rating] = 0
+        X.eliminate_zeros()
+        if implicit:
+            X.data = np.ones(X.nnz)
+    X.sort_indices()
+    row_len = np.diff(X.indptr)
+    row_sum = np.asarray(abs(X).sum(axis=1)).ravel()
+    inv = np.divide(1.0, row_sum, out=np.zeros_like(row_sum), where=row_sum != 0)
+    M = X.copy()
+    M.data = X.data * np.repeat(inv, row_len)
+    if alpha != 1.0:
+        M.data = np.power(M.data, alpha)
+    item_count = np.bincount(X.indices, minlength=X.shape[1]).astype(np.float64)
+    if beta is not None:
+        degree = np.zeros(X.shape[1])
+        degree[item_count != 0] = np.power(item_count[item_count != 0], -float(beta))
+        M.data = M.data * degree[M.indices]
+    B = X.copy()
+    B.data = np.ones(X.nnz)
+    return B, M, item_count
+
+
+def oracle_random_walk(URM, alpha, beta=None, min_rating=0, implicit=False, M=None):
+    """P3alpha (beta None) / RP3beta: the full row-wise walk
+         W[i, j] = item_count[i]^-alpha * sum_u B[u, i] * M[u, j],   W[i, i] = 0,
+    as a sparse float64 matrix BEFORE any top-K (GraphBased/P3alphaRecommender.py fit, RP3betaRecommender.py fit: Piu . Pui with
+    Piu[i, u] = (1 / item_count[i])^alpha, times degree[j]).  Built as B^T @ M, so it has the fill of the item co-occurrence graph.
+    The reference holds Pui, Piu and their product in float32 when the URM is float32; this is its float64 statement.
+    M: values to use in place of M's (same structure) -- a test hands in the float32-rounded values a device was given."""
+    B, M64, item_count = oracle_walk_inputs(URM, alpha, beta, min_rating, implicit)
+    if M is not None:
+        M = sps.csr_matrix(M, dtype=np.float64, copy=True)
+        M.sort_indices()
+        assert M.shape == M64.shape and (M.indptr == M64.indptr).all() and (M.indices == M64.indices).all(), "M: another structure"
+        M64 = M
+    row_factor = np.zeros(len(item_count))
+    row_factor[item_count != 0] = np.power(1.0 / item_count[item_count != 0], alpha)
+    W = sps.csr_matrix(sps.diags(row_factor).dot(sps.csr_matrix(B.T).dot(M64)))
+    W.sort_indices()
+    rows = np.repeat(np.arange(W.shape[0]), np.diff(W.indptr))
+    W.data[rows == W.indices] = 0.0                     # the reference zeroes the item's own cell before it ranks the row
+    W.eliminate_zeros()
+    W.sort_indices()
+    return W
+
+
+def oracle_random_walk_topk(W_full, topK, normalize_similarity=False):
+    """The reference's steps behind the walk, in its order: per ROW the topK largest cells (zeros compete, then are dropped), the
+    optional l1 normalisation of the rows, similarityMatrixTopK (per COLUMN the topK largest of the non-zero cells).  CSR float64.
+    Ties go to the lower index (the reference's are artefacts of its argsort)."""
+    W = sps.csr_matrix(W_full, dtype=np.float64)
+    n = W.shape[0]
+    k = min(int(topK), n)
+    rows, cols, vals = [], [], []
+    for i in range(n):
+        dense = W[i].toarray().ravel()
+        order = np.lexsort((np.arange(n), -dense))[:k]
+        order = order[dense[order] != 0.0]
+        v = dense[order]
+        if normalize_similarity and np.abs(v).sum() != 0:
+            v = v / np.abs(v).sum()
+        rows.extend([i] * len(order)); cols.extend(order.tolist()); vals.extend(v.tolist())
+    R = sps.csc_matrix((vals, (rows, cols)), shape=(n, n))
+    R.sort_indices()
+    rows, cols, vals = [], [], []
+    for j in range(n):
+        s, e = R.indptr[j], R.indptr[j + 1]
+        idx, v = R.indices[s:e], R.data[s:e]
+        keep = np.lexsort((idx, -v))[:k]
+        rows.extend(idx[keep].tolist()); cols.extend([j] * len(keep)); vals.extend(v[keep].tolist())
+    out = sps.csr_matrix((vals, (rows, cols)), shape=(n, n))
+    out.sort_indices()
+    return out

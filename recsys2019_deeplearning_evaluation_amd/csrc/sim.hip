@@ -925,9 +925,16 @@ void create_stream_and_walk(SimCreate &c) {
 // Real-valued data: can the column sums be kept as int64 fixed point (ds_add_u64 is 1.8x faster than ds_add_f64)?
 // Every product is at most P = max weight * max |column-side value| * max |value|; a cell sums at most N = longest
 // column of them.  Scale 2^S with P * 2^S <= 2^50 (the float64 rounding trick needs |x| < 2^51) and N * P * 2^S <= 2^62.
-// A cell is then off by at most N / 2 units of 2^-S; the smallest denominator it can meet is the smallest non-zero
-// column norm squared (normalised similarities) -- accept when that WORST-CASE error stays below 1e-6 (a tenth of the
-// parity bar; rounding errors of random sign add up to ~sqrt(N), not N), otherwise keep float64.
+// A cell is then off by at most N / 2 units of 2^-S.  What that error is measured against:
+//   normalised similarities, Euclidean distances: the smallest denominator a cell can meet, the smallest non-zero column norm
+//     squared (a distance is measured against the sum of two of them: the same bar, conservative);
+//   every other un-normalised build (the results are the sums themselves, or the sums over a denominator that does not depend on
+//     the data's scale): the smallest non-zero CELL, which is at least the smallest non-zero product -- smallest weight * smallest
+//     |value| (unit column side: the P3alpha / RP3beta walk) or * smallest |value| squared.  A column's norm says nothing here: one
+//     large entry carries it while a cell sums the column's tiny entries (values of sign-mixed data can cancel below any such
+//     bound, in float64 as well).
+// Accept when that WORST-CASE error stays below 1e-6 (a tenth of the parity bar; rounding errors of random sign add up to
+// ~sqrt(N), not N), otherwise keep float64.
 void create_fixed_point(SimCreate &c) {
     mi355rec_sim *h = c.h;
     const mi355rec_sim_config *cfg = c.cfg;
@@ -937,21 +944,42 @@ void create_fixed_point(SimCreate &c) {
     const float *row_weights = c.row_weights;
     DeviceBuffer<double> &sumsq = c.sumsq;
     if (h->acc_mode() == ACC_WIDE && !getenv("MI355REC_SIM_F64_SUMS")) {
-        DeviceBuffer<unsigned> d_vmax;
+        // (h->cfg: the set-based measures have had their `normalize` cleared)
+        const bool by_smallest_cell = !h->cfg.normalize && !c.euclid;
+        DeviceBuffer<unsigned> d_vmax, d_vmin;
         d_vmax.alloc_zero(1, s);
         hipLaunchKernelGGL(absmax_kernel, dim3(eg), dim3(eb), 0, s, h->csc_val.ptr, nnz, d_vmax.ptr);
         MI_HIP(hipGetLastError());
-        unsigned vbits = 0;
+        unsigned vbits = 0, vmin_bits = 0xFFFFFFFFu;
         d_vmax.download(&vbits, 1, s);
+        if (by_smallest_cell) {
+            d_vmin.alloc(1);
+            MI_HIP(hipMemsetAsync(d_vmin.ptr, 0xFF, sizeof(unsigned), s));
+            hipLaunchKernelGGL(absmin_nonzero_kernel, dim3(eg), dim3(eb), 0, s, h->csc_val.ptr, nnz, d_vmin.ptr);
+            MI_HIP(hipGetLastError());
+            d_vmin.download(&vmin_bits, 1, s);
+        }
         std::vector<double> sq((size_t)n_cols);
         sumsq.download(sq.data(), (size_t)n_cols, s);
         MI_HIP(hipStreamSynchronize(s));
         float vmax_f;
         memcpy(&vmax_f, &vbits, sizeof(float));
         const double vmax = (double)vmax_f;
-        double wmax = 1.0;
-        if (row_weights)
-            for (int r = 0; r < n_rows; ++r) wmax = std::max(wmax, (double)std::fabs(row_weights[r]));
+        double vmin = 0.0;                  // smallest non-zero |value| (0: none)
+        if (vmin_bits != 0xFFFFFFFFu) {
+            float vmin_f;
+            memcpy(&vmin_f, &vmin_bits, sizeof(float));
+            vmin = (double)vmin_f;
+        }
+        double wmax = 1.0, wmin = 1.0;      // wmin: smallest non-zero |weight|
+        if (row_weights) {
+            wmin = 0.0;
+            for (int r = 0; r < n_rows; ++r) {
+                const double w = (double)std::fabs(row_weights[r]);
+                wmax = std::max(wmax, w);
+                if (w > 0.0 && (wmin == 0.0 || w < wmin)) wmin = w;
+            }
+        }
         double longest = 1.0, min_sq = 0.0;
         for (int col = 0; col < n_cols; ++col) {
             longest = std::max(longest, (double)(h->csc_ptr_host[col + 1] - h->csc_ptr_host[col]));
@@ -961,10 +989,9 @@ void create_fixed_point(SimCreate &c) {
         if (prod > 0.0 && std::isfinite(prod)) {
             const int S = (int)std::floor(std::min(50.0 - std::log2(prod), 62.0 - std::log2(prod * longest)));
             const double unit = std::ldexp(1.0, -S);
-            // denominators: norm_c * norm_j >= min_sq (normalised); otherwise the results are the sums themselves, whose
-            // scale is at least the smallest non-zero product -- bounded below by min_sq as well only for single-cell
-            // columns, so the same bar is applied (conservative for everything else)
-            const double worst = 0.5 * longest * unit / std::max(min_sq, 1e-300);
+            // denominators: norm_c * norm_j >= min_sq (normalised); otherwise the smallest non-zero cell (see above)
+            const double floor_of_results = by_smallest_cell ? wmin * (cfg->unit_column_side ? 1.0 : vmin) * vmin : min_sq;
+            const double worst = 0.5 * longest * unit / std::max(floor_of_results, 1e-300);
             if (S > -1000 && S < 1000 && worst <= 1e-6) h->fixed_scale = std::ldexp(1.0, S);
         }
     }

@@ -532,6 +532,18 @@ __global__ void absmax_kernel(const float *val, size_t nnz, unsigned *out) {
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
 
+// smallest non-zero |value| (same ordering; `out` starts at 0xFFFFFFFF and stays there when every stored value is zero)
+__global__ void absmin_nonzero_kernel(const float *val, size_t nnz, unsigned *out) {
+    unsigned m = 0xFFFFFFFFu;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < nnz; i += (size_t)gridDim.x * blockDim.x) {
+        const unsigned b = __float_as_uint(fabsf(val[i]));
+        if (b) m = min(m, b);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, off));
+    if ((threadIdx.x & 63) == 0 && m != 0xFFFFFFFFu) atomicMin(out, m);
+}
+
 // CSR assembly of the result (.pyx:603-605: row = neighbour, column = source item) -- sort keys: the neighbour id of
 // every slab entry, padding entries (-1) mapped past the last row so that they sort to the end.
 __global__ void csr_keys_kernel(const int *slab_idx, size_t n, int n_cols, int *key, int *pos) {

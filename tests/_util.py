@@ -66,6 +66,57 @@ def check_topk_against_dense(idx, val, dense_col, topK, rtol=1e-5):
     assert (np.diff(got_val) <= tol).all(), "values must be non-increasing"
 
 
+# Relative error a cell of an UN-NORMALISED build may show against a float64 oracle that was given the same float32 input values, one
+# 2^-24 (half a float32 ulp) per float32 rounding on the way -- derived from the operations, not measured:
+#   builder slabs (Compute_Similarity_MI355X.compute_slabs): the float64 (or exact fixed-point) column sum is stored as float32 -- 1;
+#   walk rows (graph_based._fit_walk, W_rowwise): that store, the multiplication by row_factor and the cast to float32 -- 3 (the
+#     multiplication runs in float64 today and then costs 2^-53; its slot is kept so that the bound also covers a float32 product).
+# The float64 sum itself adds n * 2^-53 for n products of one sign, below 2^-40 for the 8 192 users a test column may have.
+# On the int64 fixed-point accumulator the gate of create_fixed_point (sim.hip) promises a worst-case 1e-6 on top of that.
+F32_ROUNDING = 2.0 ** -24
+F64_SUM_SLACK = 2.0 ** -40
+FIXED_POINT_PROMISE = 1e-6
+
+
+def per_cell_bound(accumulator_kind, f32_roundings):
+    """Relative bound of one emitted cell: `f32_roundings` float32 roundings, plus the fixed-point gate's promise where it applies."""
+    assert accumulator_kind in ("uint32", "int32-exact", "int64-fixed", "float64")
+    return f32_roundings * F32_ROUNDING + F64_SUM_SLACK + (FIXED_POINT_PROMISE if accumulator_kind == "int64-fixed" else 0.0)
+
+
+def check_topk_per_cell(idx, val, dense_col, topK, rtol):
+    """check_topk_against_dense with every tolerance taken relative to the CELL instead of to the column's largest value -- for raw sums,
+    whose cells span many decades (a bound relative to the maximum lets a cell a thousand times smaller be entirely wrong).
+
+    Same membership rule: with t = K-th largest value of the column (zeros compete, then are dropped), a cell x is in the tie class
+    of the cut when |x - t| <= rtol * max(|x|, |t|); every non-zero cell above the class must be present, nothing below it may be,
+    no zero may be emitted, the count follows, and the order is non-increasing up to the same relative band.  Every emitted value must
+    lie within rtol * |x| of the oracle's value x of its own cell.  Returns the largest relative error of the emitted values."""
+    dense_col = np.asarray(dense_col, dtype=np.float64)
+    n = len(dense_col)
+    K = min(topK, n)
+    got = idx[idx >= 0]
+    got_val = np.asarray(val[:len(got)], dtype=np.float64)
+    assert (idx[len(got):] == -1).all(), "padding must be trailing"
+    assert len(np.unique(got)) == len(got), "duplicate neighbour"
+    t = np.sort(dense_col)[::-1][K - 1]
+    band = rtol * np.maximum(np.abs(dense_col), abs(t))
+    above = (dense_col - t > band) & (dense_col != 0)
+    not_below = (dense_col - t >= -band) & (dense_col != 0)
+    assert np.isin(np.flatnonzero(above), got).all(), "a cell strictly above the K-th value is missing"
+    assert (dense_col[got] != 0).all(), "a zero similarity was emitted"
+    assert not_below[got].all(), "a cell strictly below the K-th value was emitted"
+    strict_count = int(above.sum())
+    assert strict_count <= len(got) <= max(min(K, int(not_below.sum())), strict_count)
+    want = dense_col[got]
+    err = np.abs(got_val - want) / np.abs(want) if len(got) else np.zeros(0)
+    worst = float(err.max()) if len(got) else 0.0
+    assert worst <= rtol, "cell %d: %.9g against %.9g, relative error %.3g > %.3g" % (
+        got[int(err.argmax())], got_val[int(err.argmax())], want[int(err.argmax())], worst, rtol)
+    assert (np.diff(got_val) <= 2 * rtol * np.abs(got_val[:-1])).all(), "values must be non-increasing"
+    return worst
+
+
 def csr_columns_as_slabs(W, topK):
     """csr/csc matrix with <= topK entries per column -> (idx, val) slabs sorted by descending value."""
     W = sps.csc_matrix(W)

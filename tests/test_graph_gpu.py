@@ -53,3 +53,294 @@ def test_implicit_mode_is_inside_the_reference_tie_class(gpu):
         idx = -np.ones(10, np.int32); val = np.zeros(10, np.float32)
         idx[:len(order)] = row.indices[order]; val[:len(order)] = row.data[order]
         check_topk_against_dense(idx, val, S[i], 10, 1e-5)
+
+
+# ------------------------------------------------------------------------------------------------------------
+#   The walk on every route of the builder, cell by cell against the float64 oracle (oracle.oracle_random_walk, checked against the
+#   reference by tests/test_graph_spec.py).  The oracle is handed the SAME float32 M the device gets (graph_based.walk_matrix), so
+#   what remains is the device's own arithmetic: _util.per_cell_bound.
+# ------------------------------------------------------------------------------------------------------------
+import os
+import re
+
+import scipy.sparse as sps
+
+from oracle import oracle as O
+from recsys2019_deeplearning_evaluation_amd import Compute_Similarity_MI355X
+from recsys2019_deeplearning_evaluation_amd.graph_based import walk_builder, walk_matrix
+from recsys2019_deeplearning_evaluation_amd.synthetic import synthetic_urm
+from _util import F32_ROUNDING, check_topk_per_cell, per_cell_bound
+import graph_cases as G
+
+WIDE_KINDS = ("int64-fixed", "float64")         # 8-byte accumulator cells
+_cache = {}
+
+
+def _ml1m():
+    if "ml1m" not in _cache:
+        _cache["ml1m"] = named_urm("ml1m", "real", scale=0.25)
+    return _cache["ml1m"]
+
+
+def _oracle_walk(name, X, alpha, beta, min_rating=0, implicit=False):
+    """The full float64 walk over the float32 M of graph_based.walk_matrix; computed once per (URM, arguments) and left unchanged."""
+    key = (name, alpha, beta, min_rating, implicit)
+    if key not in _cache:
+        F = sps.csr_matrix(X, dtype=np.float32, copy=True)      # what fit() leaves in URM_train
+        if min_rating > 0:
+            F.data[F.data < min_rating] = 0
+            F.eliminate_zeros()
+            if implicit:
+                F.data[:] = 1
+        M, _ = walk_matrix(F, alpha, beta)
+        _cache[key] = O.oracle_random_walk(X, alpha, beta, min_rating, implicit, M=M)
+    return _cache[key]
+
+
+def _fit(X, alpha, beta, topK, normalize_similarity=False, **kw):
+    rec = (P3alphaRecommender if beta is None else RP3betaRecommender)(X.copy(), verbose=False)
+    rec.fit(topK=topK, alpha=alpha, normalize_similarity=normalize_similarity, **(kw if beta is None else dict(kw, beta=beta)))
+    return rec
+
+
+def _row_slab(W, i, topK):
+    """Row i of W_rowwise as a -1 padded, value-descending slab.  (Sorted here: the l1 normalisation of fit() goes through SciPy's
+    abs(), which puts the rows of W_rowwise into index order in place; the builder's own order is checked on its slabs below.)"""
+    s, e = W.indptr[i], W.indptr[i + 1]
+    order = np.lexsort((W.indices[s:e], -W.data[s:e]))
+    idx = -np.ones(topK, np.int32); val = np.zeros(topK, np.float64)
+    idx[:e - s] = W.indices[s:e][order]; val[:e - s] = W.data[s:e][order]
+    return idx, val
+
+
+def _check_rows_per_cell(W_rowwise, walk, topK, rtol, rows=None):
+    """Every (or every listed) row of the pre-cut walk against the oracle, cell by cell; returns the largest relative error."""
+    W = W_rowwise.tocsr()
+    walk = walk.tocsr()
+    worst = 0.0
+    for i in (range(W.shape[0]) if rows is None else rows):
+        idx, val = _row_slab(W, i, topK)
+        worst = max(worst, check_topk_per_cell(idx, val, walk[i].toarray().ravel(), topK, rtol))
+    print("per-cell: worst relative error %.3g (bound %.3g)" % (worst, rtol))
+    return worst
+
+
+def _same_rows(A, B, rtol=None):
+    """Identical neighbour ids in identical order; values equal, or within rtol of the largest."""
+    A, B = A.tocsr(), B.tocsr()
+    np.testing.assert_array_equal(A.indptr, B.indptr)
+    np.testing.assert_array_equal(A.indices, B.indices)
+    if rtol is None:
+        np.testing.assert_array_equal(A.data, B.data)
+    else:
+        assert np.abs(A.data - B.data).max() <= rtol * np.abs(B.data).max()
+
+
+def test_search_range_fixture_parity_and_per_cell_walk(gpu):
+    """Every case of graph_based_search.npz (the reference's own W_sparse over the search range) through the two recommenders: the
+    support through both cuts with their tie classes, the values within 1e-5 of the row's largest -- against the reference's cells and
+    against the oracle's --, and the pre-cut W_rowwise cell by cell against the oracle."""
+    X, cases = G.load_cases()
+    for case in cases:
+        kw, arg = case["kw"], G.walk_arguments(case)
+        rec = (P3alphaRecommender if case["cls"] == "P3" else RP3betaRecommender)(X.copy(), verbose=False)
+        rec.fit(**kw)
+        walk = _oracle_walk("search", X, arg["alpha"], arg["beta"], arg["min_rating"], arg["implicit"])
+        bound = per_cell_bound(rec.similarity_accumulator[0], 3)
+        _check_rows_per_cell(rec.W_rowwise, walk, min(kw["topK"], X.shape[1]), bound)
+        # behind the row cut: the float64 division by the row's sum (its cells off by `bound`) and similarityMatrixTopK's float32 cast;
+        # two neighbours at a cut may each be off by that
+        cut = 2 * (2 * bound + F32_ROUNDING)
+        G.check_w_sparse_against_walk(rec.W_sparse, walk, kw["topK"], kw["normalize_similarity"], rtol=cut, value_atol_of_row_max=1e-5)
+        got, want = rec.W_sparse.toarray().astype(np.float64), case["W"].toarray().astype(np.float64)
+        both = (got != 0) & (want != 0)
+        row_max = np.abs(want).max(axis=1, keepdims=True) * np.ones_like(want)
+        assert (np.abs(got - want)[both] <= 1e-5 * row_max[both]).all(), case["index"]
+        # the reference's support passes the same check with ITS tie class (tests/test_graph_spec.py): both lie in one class
+        assert not np.isnan(got).any()
+
+
+def test_fixed_point_gate_bounds_the_smallest_cell_of_an_unnormalised_build(gpu, monkeypatch):
+    """normalize=False: a column's norm can be carried by one large entry while a cell of the result sums the column's tiny ones.  64 x 8:
+    a unit diagonal, column 0 all ones over rows 8 .. 39, the other columns 3e-13 there -- norms of 1 everywhere, cells of 32 * 3e-13 (unit
+    column side and plain products against column 0) and of 32 * 9e-26 (plain products among the others).  A scale of 2^50 rounds
+    3e-13 * 2^50 = 337.8 to 338 (6.8e-4 off) and 9e-26 * 2^50 to 0: either the accumulator is float64 or every cell meets the bound
+    that the fixed-point gate promises.  (Measured on the library before the gate was repaired: "int64-fixed" at scale 2^50 in both
+    modes; with the unit column side 49 of the 56 cells off by 6.81e-4; without it the 14 cells against column 0 off by the same
+    6.81e-4 and the 42 cells among columns 1 .. 7 zero, hence dropped.  Now: float64 in both modes, worst relative error 1.8e-8.)"""
+    monkeypatch.delenv("MI355REC_SIM_F64_SUMS", raising=False)
+    M = np.zeros((64, 8), np.float32)
+    M[np.arange(8), np.arange(8)] = 1.0
+    M[8:40, 0] = 1.0
+    M[8:40, 1:] = 3e-13
+    M64 = M.astype(np.float64)
+    for unit in (True, False):
+        dev = Compute_Similarity_MI355X(sps.csr_matrix(M), topK=7, shrink=0, normalize=False, similarity="cosine", unit_column_side=unit)
+        kind, scale = dev.accumulator_info()
+        idx, val, _ = dev.compute_slabs()
+        dev.close()
+        S = ((M64 != 0).astype(np.float64) if unit else M64).T @ M64
+        np.fill_diagonal(S, 0.0)
+        print("unit_column_side=%s: accumulator %s, scale %g" % (unit, kind, scale))
+        assert kind in WIDE_KINDS
+        for c in range(8):
+            check_topk_per_cell(idx[c], val[c], S[c], 7, per_cell_bound(kind, 1))
+
+
+@pytest.mark.parametrize("alpha,beta,kind", [(1.0, None, "int64-fixed"), (2.0, None, "int64-fixed"), (1.0, 0.6, "int64-fixed"),
+                                             (0.4, 0.3, "int64-fixed"), (2.0, 2.0, "float64")])
+def test_ordinary_walks_stay_on_the_fixed_point_accumulator(gpu, alpha, beta, kind, monkeypatch):
+    """The gate's bound on the smallest cell must not take ordinary walks off int64 fixed point (the faster accumulator); (2, 2), whose
+    values span twelve decades, is refused."""
+    monkeypatch.delenv("MI355REC_SIM_F64_SUMS", raising=False)
+    M, _ = walk_matrix(_ml1m(), alpha, beta)
+    dev = walk_builder(M, 50)
+    got = dev.accumulator_info()
+    dev.close()
+    assert got[0] == kind, got
+
+
+@pytest.mark.parametrize("alpha,beta", [(1.0, 0.6), (2.0, None)])
+def test_walk_on_both_accumulators(gpu, alpha, beta, monkeypatch):
+    """int64 fixed point (the default here) and float64 sums (forced): identical neighbours, values within 2e-6, each build cell by cell."""
+    X = _ml1m()
+    walk = _oracle_walk("ml1m", X, alpha, beta)
+    built = {}
+    for forced in (False, True):
+        if forced:
+            monkeypatch.setenv("MI355REC_SIM_F64_SUMS", "1")
+        else:
+            monkeypatch.delenv("MI355REC_SIM_F64_SUMS", raising=False)
+        rec = _fit(X, alpha, beta, 50)
+        kind = rec.similarity_accumulator[0]
+        assert kind == ("float64" if forced else "int64-fixed")
+        _check_rows_per_cell(rec.W_rowwise, walk, 50, per_cell_bound(kind, 3))
+        built[forced] = rec.W_rowwise
+    _same_rows(built[False], built[True], rtol=2e-6)
+
+
+def test_walk_refused_by_the_gate_is_exact_down_to_its_smallest_cells(gpu, monkeypatch):
+    """(alpha, beta) = (2, 2): float64 by refusal; the cells of the whole walk (topK = all items) span more than six decades and each
+    one meets the float64 bound."""
+    monkeypatch.delenv("MI355REC_SIM_F64_SUMS", raising=False)
+    X = _ml1m()
+    walk = _oracle_walk("ml1m", X, 2.0, 2.0)
+    assert walk.data.min() < 1e-6 * walk.data.max()        # (the oracle's cells: what this test is about)
+    rec = _fit(X, 2.0, 2.0, X.shape[1])
+    assert rec.similarity_accumulator[0] == "float64"
+    assert rec.W_rowwise.nnz == walk.nnz                   # every non-zero cell is emitted
+    _check_rows_per_cell(rec.W_rowwise, walk, X.shape[1], per_cell_bound("float64", 3))
+
+
+def test_walk_with_columns_split_over_workgroups(gpu, monkeypatch):
+    X = _ml1m()
+    walk = _oracle_walk("ml1m", X, 1.0, 0.6)
+    built = {}
+    for min_part in ("64", "1000000"):
+        monkeypatch.setenv("MI355REC_SIM_MIN_PART_USERS", min_part)
+        rec = _fit(X, 1.0, 0.6, 50)
+        n_items, n_split, n_parts = rec.similarity_schedule
+        if min_part == "64":
+            assert n_split > 0 and n_parts >= 2 * n_split and n_items == X.shape[1] - n_split + n_parts, rec.similarity_schedule
+        else:
+            assert n_split == 0, rec.similarity_schedule
+        _check_rows_per_cell(rec.W_rowwise, walk, 50, per_cell_bound(rec.similarity_accumulator[0], 3))
+        built[min_part] = rec.W_rowwise
+    _same_rows(built["64"], built["1000000"], rtol=2e-6)
+
+
+def test_walk_over_two_accumulator_tiles(gpu, monkeypatch):
+    """18 000 items on 8-byte cells: two tiles (MAX_TILE_F64 of csrc/sim_kernels.cuh, which create_tiles_and_row_centring of sim.hip
+    applies to every accumulator that is not 4-byte counts or exact int32 sums) and the per-tile candidates merged.  Every seventh row
+    cell by cell; a row range equals the same rows of the full build."""
+    monkeypatch.delenv("MI355REC_SIM_F64_SUMS", raising=False)
+    X = synthetic_urm(1500, 18000, 120000, 5, 400, seed=7, values="real")
+    header = os.path.join(G.ROOT, "recsys2019_deeplearning_evaluation_amd", "csrc", "sim_kernels.cuh")
+    max_tile_f64 = int(re.search(r"constexpr int MAX_TILE_F64 = (\d+);", open(header).read()).group(1))
+    assert max_tile_f64 < X.shape[1] <= 2 * max_tile_f64
+    M, item_count = walk_matrix(X, 1.0, 0.6)
+    dev = walk_builder(M, 40)
+    kind = dev.accumulator_info()[0]
+    assert kind in WIDE_KINDS                              # 8-byte cells
+    idx, val, _ = dev.compute_slabs()
+    part_idx, part_val, s0 = dev.compute_slabs(8000, 8100)
+    dev.close()
+    assert s0 == 8000
+    np.testing.assert_array_equal(part_idx, idx[8000:8100])
+    np.testing.assert_array_equal(part_val, val[8000:8100])
+    # the builder's slabs hold the plain sums: the oracle's rows without Piu's factor (alpha = 1: the item's count)
+    walk = sps.diags(item_count).dot(O.oracle_random_walk(X, 1.0, 0.6, M=M)).tocsr()
+    worst = 0.0
+    for i in range(0, X.shape[1], 7):
+        worst = max(worst, check_topk_per_cell(idx[i], val[i], walk[i].toarray().ravel(), 40, per_cell_bound(kind, 1)))
+    print("per-cell: worst relative error %.3g" % worst)
+
+
+def test_walk_selection_routes(gpu, monkeypatch):
+    """MI355REC_SIM_FAST_TOPK on and off: the same neighbours, order and values, bit for bit.  The threshold-first selection serves
+    4-byte cells only (fast_topk_for, csrc/sim_plan.h): the real-valued walk never takes it, the alpha = 0 P3alpha walk (all ones:
+    counts) does."""
+    X = _ml1m()
+    for alpha, beta, fast in ((1.0, 0.6, False), (0.0, None, True)):
+        built = {}
+        for switch in ("1", "0"):
+            monkeypatch.setenv("MI355REC_SIM_FAST_TOPK", switch)
+            rec = _fit(X, alpha, beta, 10)
+            built[switch] = (rec.W_rowwise, rec.similarity_selection)
+        monkeypatch.delenv("MI355REC_SIM_FAST_TOPK")
+        _same_rows(built["1"][0], built["0"][0])
+        assert built["0"][1] == (0, 0, 0)
+        info = built["1"][1]
+        assert (info[0] > 0 and info[2] == 0) if fast else info == (0, 0, 0), info
+        _check_rows_per_cell(built["1"][0], _oracle_walk("ml1m", X, alpha, beta), 10, per_cell_bound(rec.similarity_accumulator[0], 3))
+
+
+def test_walk_with_topk_beyond_the_lds_selection(gpu):
+    """topK = 5000 of 6000 items: dense columns and a segmented sort instead of the in-LDS selection."""
+    X = synthetic_urm(800, 6000, 24000, 5, 600, seed=14, values="real", zipf_exponent=0.5)
+    M, item_count = walk_matrix(X, 1.0, 0.6)
+    dev = walk_builder(M, 5000)
+    kind = dev.accumulator_info()[0]
+    idx, val, s0 = dev.compute_slabs(2100, 2400)
+    dev.close()
+    assert idx.shape == (300, 5000) and s0 == 2100
+    walk = sps.diags(item_count).dot(O.oracle_random_walk(X, 1.0, 0.6, M=M)).tocsr()
+    for i in range(2100, 2400, 13):
+        check_topk_per_cell(idx[i - 2100], val[i - 2100], walk[i].toarray().ravel(), 5000, per_cell_bound(kind, 1))
+
+
+def test_alpha_zero_counts_co_occurrences(gpu):
+    """alpha = 0 (accepted here, refused by the reference's SciPy .power): every value of P3alpha's M is 1, the builder counts in uint32
+    cells and the walk is the integer co-occurrence count times row_factor = n_i^-0 = 1 -- exactly.  RP3beta's M is degree^-beta."""
+    for name, X in (("search", G.load_cases()[0]), ("ml1m", _ml1m())):
+        topK = 20
+        rec = _fit(X, 0.0, None, topK)
+        assert rec.similarity_accumulator[0] == "uint32"
+        Xb = (X != 0).astype(np.float64)
+        counts = (Xb.T @ Xb).toarray()
+        np.fill_diagonal(counts, 0.0)
+        assert (_oracle_walk(name, X, 0.0, None).toarray() == counts).all()
+        assert (rec.W_rowwise.data == np.round(rec.W_rowwise.data)).all()
+        W = rec.W_rowwise.tocsr()
+        for i in range(X.shape[1]):
+            check_topk_per_cell(*_row_slab(W, i, topK), counts[i], topK, 0.0)
+        rec = _fit(X, 0.0, 0.6, topK)
+        assert rec.similarity_accumulator[0] in WIDE_KINDS
+        _check_rows_per_cell(rec.W_rowwise, _oracle_walk(name, X, 0.0, 0.6), topK, per_cell_bound(rec.similarity_accumulator[0], 3))
+
+
+@pytest.mark.parametrize("normalize_similarity", [False, True])
+def test_degenerate_rows(gpu, normalize_similarity):
+    """topK past the row length on the fixture URM: cold items keep empty rows and columns, rows without a sum survive the
+    normalisation without NaN, the single-user item walks to everything its user holds."""
+    X, _ = G.load_cases()
+    for rec in (_fit(X, 0.4, None, 1000, normalize_similarity), _fit(X, 1.0, 0.6, 1000, normalize_similarity)):
+        W = rec.W_sparse.toarray()
+        assert np.isfinite(W).all() and np.isfinite(rec.W_rowwise.data).all()
+        cold = list(G.COLD_ITEMS)
+        assert (W[cold] == 0).all() and (W[:, cold] == 0).all()
+        warm = np.setdiff1d(np.arange(X.shape[1]), cold)
+        assert ((W[warm] != 0).sum(axis=1) == len(warm) - 1).all()          # FULL_USER links every pair of warm items
+        assert W.diagonal().max() == 0
+        if normalize_similarity:
+            np.testing.assert_allclose(W[warm].sum(axis=1), 1.0, rtol=(len(warm) + 1) * F32_ROUNDING)
