@@ -610,6 +610,35 @@ int mi355rec_spscorer_recommend_candidates(mi355rec_spscorer_t h, const int32_t 
 int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 
+/* Similarity models whose weights are a DENSE array: scores[u] = A[u, :] . B, A (n_users x n_mid) CSR float32, B (n_mid x n_items)
+ * float32 row-major -- Base/BaseSimilarityMatrixRecommender.py:73-92 with a W_sparse that is an ndarray, what
+ * EASE_R_Recommender.fit(topK=None) leaves (EASE_R/EASE_R_Recommender.py:40-82).  Every score is SciPy's csr @ ndarray bit for bit:
+ * from +0.0f, over the row's stored cells IN STORAGE ORDER (the indices are used as given, never sorted), acc = acc + (a * B[i][j])
+ * in float32 with the product rounded before the add.  The same call gives the same bytes every time.  B is not checked for
+ * non-finite values: they are scored as IEEE arithmetic gives them, and a NaN score is never listed.  Filtering and ranking as
+ * mi355rec_scorer_recommend.
+ * create: B (nullable: zero weights until update / set_from_ease) is copied to the device; MI355REC_E_INVALID, before anything is
+ * allocated or launched, when it does not fit the device's free memory, and for column ids outside their range. */
+typedef struct mi355rec_dscorer *mi355rec_dscorer_t;
+int mi355rec_dscorer_create(mi355rec_dscorer_t *out, int32_t n_users, int32_t n_mid, int32_t n_items, const int32_t *a_indptr,
+                            const int32_t *a_indices, const float *a_data, const float *B, const int32_t *seen_indptr,
+                            const int32_t *seen_indices);
+/* A new B of the same shape; nothing is reallocated. */
+int mi355rec_dscorer_update(mi355rec_dscorer_t h, const float *B);
+/* B <- the weights of an EASE handle after a successful invert (the cells mi355rec_ease_get_dense downloads), device to device.
+ * The scorer must be n_items x n_items for the handle's n_items.  get_stats afterwards: call_ms = kernel_ms = the copy. */
+int mi355rec_dscorer_set_from_ease(mi355rec_dscorer_t h, mi355rec_ease_t ease);
+/* get_stats afterwards: kernel_ms = the scoring kernel, call_ms = scoring + ranking, algorithmic_bytes = 4 * n_items * (stored cells of
+ * the batch's rows of A): every stored cell streams one row of B. */
+int mi355rec_dscorer_recommend(mi355rec_dscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
+                               const uint8_t *item_allowed, int32_t *ranked, float *scores);
+/* As mi355rec_scorer_recommend_candidates; a candidate's score is bitwise the cell of the full row. */
+int mi355rec_dscorer_recommend_candidates(mi355rec_dscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
+                                          const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
+                                          const uint8_t *item_allowed, int32_t *ranked);
+int mi355rec_dscorer_get_stats(mi355rec_dscorer_t h, mi355rec_stats *stats);
+void mi355rec_dscorer_destroy(mi355rec_dscorer_t h);
+
 /* ------------------------------------------------------------------------------------------------------
  * Non-personalized models: one vector of item scores for every user  (Base/NonPersonalizedRecommender.py:30-43,119-132
  * _compute_item_score of TopPop / GlobalEffects repeats it per user; Base/BaseRecommender.py:131-222 recommend filters and ranks)
@@ -693,6 +722,8 @@ int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, in
                                const uint8_t *item_allowed);
 int mi355rec_eval_add_itemscorer(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                  const uint8_t *item_allowed);
+int mi355rec_eval_add_dscorer(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                              const uint8_t *item_allowed);
 /* Negative-sample evaluation (Evaluator.py:455-539 EvaluatorNegativeItemSample): the candidate rows of ALL n_users users as CSR
  * (indptr[n_users + 1]; item ids strictly ascending inside a row, else MI355REC_E_INVALID), uploaded once per evaluator.
  * MI355REC_E_UNSUPPORTED when a row holds more than 4096 items or the lists are more than 4096 wide. */
@@ -705,6 +736,8 @@ int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t
                                           const uint8_t *item_allowed);
 int mi355rec_eval_add_itemscorer_candidates(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                             const uint8_t *item_allowed);
+int mi355rec_eval_add_dscorer_candidates(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                         const uint8_t *item_allowed);
 /* sums[c * MI355REC_EVAL_VALUES + v]: value v summed over the evaluated users in a fixed order (the last one is the covered-user
  * count); item_counts[c * n_items + i]: times item i was recommended within cutoff c (the recommended_counter of
  * metrics.py:284-286, 762-769). */

@@ -199,6 +199,13 @@ SIGNATURES = {
     "mi355rec_spscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mi355rec_spscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_spscorer_destroy": (None, [_vp]),
+    "mi355rec_dscorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32] + [_vp] * 6),
+    "mi355rec_dscorer_update": (C.c_int, [_vp, _vp]),
+    "mi355rec_dscorer_set_from_ease": (C.c_int, [_vp, _vp]),
+    "mi355rec_dscorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mi355rec_dscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "mi355rec_dscorer_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
+    "mi355rec_dscorer_destroy": (None, [_vp]),
     "mi355rec_itemscorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp]),
     "mi355rec_itemscorer_create_resident": (C.c_int, [C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, _i64]),
     "mi355rec_itemscorer_update": (C.c_int, [_vp, _vp]),
@@ -218,6 +225,8 @@ SIGNATURES = {
     "mi355rec_eval_add_scorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_spscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_itemscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_dscorer": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "mi355rec_eval_add_dscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_set_candidates": (C.c_int, [_vp, _vp, _vp]),
     "mi355rec_eval_add_scorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_add_spscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

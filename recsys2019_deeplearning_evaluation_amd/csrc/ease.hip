@@ -500,6 +500,19 @@ extern "C" int mi355rec_ease_get_dense(mi355rec_ease_t h, float *W, int64_t ld) 
     });
 }
 
+// what the dense scorer (densescore.hip) copies its weights from, device to device: the cells mi355rec_ease_get_dense downloads
+void mi355rec::ease_weights_device(mi355rec_ease *h, const float **W, int64_t *ld, int *n) {
+    hipStream_t s = h->stream;
+    h->call_timer.start(s);
+    const bool scaled = ensure_weights(h);
+    h->call_timer.stop(s);
+    MI_HIP(hipStreamSynchronize(s));
+    if (scaled) h->topk_ms = h->call_timer.elapsed_ms();
+    *W = h->A.ptr;
+    *ld = h->npad;
+    *n = h->n;
+}
+
 extern "C" int mi355rec_ease_get_topk(mi355rec_ease_t h, int32_t topK, int32_t *idx, float *val) {
     return guarded([&] {
         MI_REQUIRE(h && idx && val, "NULL argument");

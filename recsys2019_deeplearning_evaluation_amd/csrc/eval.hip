@@ -413,6 +413,11 @@ extern "C" int mi355rec_eval_add_itemscorer(mi355rec_eval_t h, mi355rec_itemscor
     return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue); });
 }
 
+extern "C" int mi355rec_eval_add_dscorer(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
+                                         const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, dscorer_enqueue); });
+}
+
 // Negative-sample evaluation (Evaluator.py:455-539, EvaluatorNegativeItemSample): every user ranks the candidates of its row only.
 extern "C" int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *indptr, const int32_t *indices) {
     return guarded([&] {
@@ -458,6 +463,11 @@ extern "C" int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec
 extern "C" int mi355rec_eval_add_itemscorer_candidates(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n,
                                                        int32_t remove_seen, const uint8_t *item_allowed) {
     return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue_candidates); });
+}
+
+extern "C" int mi355rec_eval_add_dscorer_candidates(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n,
+                                                    int32_t remove_seen, const uint8_t *item_allowed) {
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, dscorer_enqueue_candidates); });
 }
 
 extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts) {

@@ -1,5 +1,6 @@
-// score.h -- the two scorer handles and the "score + rank on the handle's stream" half of mi355rec_scorer_recommend /
-// mi355rec_spscorer_recommend (score.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists
+// score.h -- the scorer handles (factor, sparse-similarity and -- densescore.hip -- dense-similarity models) and the "score + rank on
+// the handle's stream" half of mi355rec_scorer_recommend / mi355rec_spscorer_recommend (score.hip) and mi355rec_dscorer_recommend
+// (densescore.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists
 // where these leave them; and the same for candidate rows (cand.hip: mi355rec_*scorer_recommend_candidates, the negative-sample
 // evaluator).
 #pragma once
@@ -50,6 +51,16 @@ struct mi355rec_spscorer : mi355rec::ScorerHandle {  // `timer`: the scoring dis
     ~mi355rec_spscorer() { shutdown(); }
 };
 
+struct mi355rec_dscorer : mi355rec::ScorerHandle {   // densescore.hip.  `timer`: the scoring dispatch; `call_timer`: scoring + ranking
+    int n_mid = 0, unroll = 0;
+    int64_t ldb = 0;                                 // floats between two rows of B (n_items rounded up to 4)
+    mi355rec::DeviceBuffer<int> a_ptr, a_idx;        // A as stored: the order of a row's cells is the order of the sum
+    mi355rec::DeviceBuffer<float> a_val, B;
+    std::vector<int> a_ptr_host;                     // (the stats count the stored cells of a batch's profiles)
+
+    ~mi355rec_dscorer() { shutdown(); }
+};
+
 namespace mi355rec {
 
 struct Ranking {
@@ -63,6 +74,17 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
                        bool keep_scores);
 Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                          bool keep_scores);
+Ranking dscorer_enqueue(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                        bool keep_scores);
+// What a scorer that writes full score rows itself (densescore.hip) takes from score.hip (host functions): room for n rows of
+// h->scores and n lists of h->ranked (grown after the stream has drained), and scorer_enqueue's filter + ranking of those rows --
+// score_rank_kernel where score_row_fits_lds, the WideRanker otherwise; keep_scores leaves the filtered rows in h->scores.
+void grow_score_rows(ScorerHandle *h, int n, int cutoff);
+void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                       bool keep_scores);
+// ease.hip: the weights W = P / (-diag P) of an inverted matrix where they stand in HBM (n x n floats, row pitch *ld), scaled now if
+// they were not yet; returns with the handle's stream drained.  MI355REC_E_INVALID without a successful invert.
+void ease_weights_device(mi355rec_ease *h, const float **W, int64_t *ld, int *n);
 // ---- candidate rows: each user ranks a short list of items of its own (Evaluator.py:455-539, EvaluatorNegativeItemSample) ----------
 constexpr int CAND_MAX = 4096;          // longest candidate row: one block_rank_emit (topk.cuh) over the whole row
 
@@ -86,6 +108,8 @@ Ranking scorer_enqueue_candidates(mi355rec_scorer_t h, const int *users, int n, 
                                   const CandidateRows &rows);
 Ranking spscorer_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
                                     const unsigned char *allowed, const CandidateRows &rows);
+Ranking dscorer_enqueue_candidates(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                   const CandidateRows &rows);
 // what cand.hip takes from score.hip (host functions): whether a score row of n_items floats is ranked in LDS at this cutoff, and
 // spscorer_enqueue's accumulation of rows that are not -- h->scores[b][n_items] = A[users[b], :] . B, zeroed first, unfiltered, not
 // ranked; the caller has grown h->scores.

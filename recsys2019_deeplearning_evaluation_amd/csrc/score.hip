@@ -390,27 +390,23 @@ void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const floa
     MI_HIP(hipGetLastError());
 }
 
-// The score + rank half of mi355rec_scorer_recommend: enqueued on the scorer's stream, user ids and the item mask already in
-// device memory; the ranked lists stay in h->ranked.  Buffers only grow after the stream has drained (a caller that does not
-// synchronise between blocks -- the holdout evaluator -- may still have kernels reading the old ones).
-Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                       bool keep_scores) {
-    hipStream_t s = h->stream;
+// Room for n score rows and their lists.  Buffers only grow after the stream has drained (a caller that does not synchronise between
+// blocks -- the holdout evaluator -- may still have kernels reading the old ones).
+void grow_score_rows(ScorerHandle *h, int n, int cutoff) {
     const bool wide = !fits_lds_rank(h->n_items, cutoff);
     if (h->ranked.count < (size_t)n * cutoff || h->scores.count < (size_t)n * h->n_items ||
         (wide && h->wide.capacity < (size_t)n * h->n_items)) {
-        MI_HIP(hipStreamSynchronize(s));
+        MI_HIP(hipStreamSynchronize(h->stream));
         if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
         if (h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
     }
-    h->call_timer.start(s);
-    ScoreParams sp{};
-    sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
-    sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
-    sp.users = users; sp.n_batch = n; sp.scores = h->scores.ptr;
-    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->timer.t0,
-                          h->timer.t1, 0, sp);
-    if (!wide) {
+}
+
+// The filter + rank half of a full-row scorer: h->scores[n][n_items], unfiltered, -> h->ranked[n][cutoff].
+void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                       bool keep_scores) {
+    hipStream_t s = h->stream;
+    if (fits_lds_rank(h->n_items, cutoff)) {
         RankParams rp{};
         rp.n_items = h->n_items; rp.n_pad = (h->n_items + 3) & ~3; rp.cutoff = cutoff;
         rp.remove_seen = remove_seen;
@@ -426,6 +422,22 @@ Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff,
                      h->ranked.ptr);
     }
     MI_HIP(hipGetLastError());
+}
+
+// The score + rank half of mi355rec_scorer_recommend: enqueued on the scorer's stream, user ids and the item mask already in
+// device memory; the ranked lists stay in h->ranked.
+Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                       bool keep_scores) {
+    hipStream_t s = h->stream;
+    grow_score_rows(h, n, cutoff);
+    h->call_timer.start(s);
+    ScoreParams sp{};
+    sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
+    sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
+    sp.users = users; sp.n_batch = n; sp.scores = h->scores.ptr;
+    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->timer.t0,
+                          h->timer.t1, 0, sp);
+    rank_rows_enqueue(h, users, n, cutoff, remove_seen, allowed, keep_scores);
     h->call_timer.stop(s);
     return Ranking{h->ranked.ptr, s};
 }

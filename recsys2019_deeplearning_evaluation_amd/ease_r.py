@@ -148,12 +148,25 @@ class MI355XEase(N.Handle):
 class _EASELogic:
     """Drop-in for the reference's EASE_R_Recommender (EASE_R_Recommender.py:20) with the same `fit(topK=None, l2_norm=1e3,
     normalize_matrix=False, verbose=True)` and the same `W_sparse` (float32 ndarray when topK is None, otherwise a csr_matrix).
-    `fit_info` says where the inverse ran ("device", or "host" with the reason and the elimination step that refused)."""
+    `fit_info` says where the inverse ran ("device", or "host" with the reason and the elimination step that refused) and where the
+    model is scored ("scoring").  `dense_scoring` decides that for the dense W of topK=None: "host" (the default: the recommender
+    base multiplies on the host) or "device" (MI355XDenseScorer, the same scores bit for bit).  A sparse W is
+    scored by the device sparse scorer either way."""
 
     RECOMMENDER_NAME = "EASE_R_MI355X_Recommender"         # (saved models and logs tell the two classes apart)
 
-    def __init__(self, URM_train, verbose=True):
+    def __init__(self, URM_train, verbose=True, dense_scoring="host"):
+        if dense_scoring not in ("host", "device"):
+            raise ValueError('dense_scoring must be "host" or "device", got {!r}'.format(dense_scoring))
+        if dense_scoring == "device" and not isinstance(self, GpuSimilarityScoringMixin):
+            raise ValueError('dense_scoring="device" needs the device-scoring mixin (reference_binding.bind(..., device_scoring=True))')
         super(_EASELogic, self).__init__(URM_train, verbose=verbose)
+        self.dense_scoring = dense_scoring
+
+    def _scoring_now(self):
+        if isinstance(self, _ScoringMixin) and (self.device_scorable() or self.dense_device_scorable()):
+            return "device"
+        return "host"
 
     def fit(self, topK=None, l2_norm=1e3, normalize_matrix=False, verbose=True):
         self.verbose = verbose
@@ -183,7 +196,9 @@ class _EASELogic:
                     except NotImplementedError:         # a column or a topK beyond the in-LDS selection: rank the dense W on the host
                         weights = ease.get_dense()
                 else:
-                    self.W_sparse = ease.get_dense()
+                    self.W_sparse = ease.get_dense()         # (the attribute is the reference's: it is downloaded in either mode)
+                    if self.dense_scoring == "device":       # the scorer takes the weights where they stand: no second trip over PCIe
+                        self._get_dense_scorer(weights_from=ease)
                 info["topk_ms"] = ease.fit_info()["topk_ms"]
             except FloatingPointError as exc:
                 # not positive definite.  The failed elimination has destroyed the matrix: the Gram matrix is built again (milliseconds)
@@ -204,13 +219,18 @@ class _EASELogic:
             if ease is not None:
                 ease.close()
             builder.close()
-        info.update(fill_s=t_filled - t_start, invert_s=t_inverted - t_filled, finish_s=time.perf_counter() - t_inverted)
+        if getattr(self, "_dense_scorer", None) is not None and not self.dense_device_scorable():
+            self._dense_scorer.close()              # (a sparse W after a dense one: n_items^2 floats of HBM go back)
+            self._dense_scorer = self._dense_scorer_src = None
+        info.update(fill_s=t_filled - t_start, invert_s=t_inverted - t_filled, finish_s=time.perf_counter() - t_inverted,
+                    scoring=self._scoring_now())
         self.fit_info = info
 
     def recommend(self, user_id_array, *args, **kwargs):
-        """The device sparse scorer for a sparse W_sparse; the dense array of topK=None is scored by the recommender base on the host
-         -- the device mixin, where the class has one, is stepped over."""
-        if isinstance(self, _ScoringMixin) and not self.device_scorable():
+        """The device sparse scorer for a sparse W_sparse.  The dense array of topK=None goes to the device dense scorer with
+        dense_scoring="device" (DESIGN section 16); otherwise it is scored by the recommender base on the host -- the device mixin,
+        where the class has one, is stepped over."""
+        if isinstance(self, _ScoringMixin) and not self.device_scorable() and not self.dense_device_scorable():
             return super(_ScoringMixin, self).recommend(user_id_array, *args, **kwargs)
         return super(_EASELogic, self).recommend(user_id_array, *args, **kwargs)
 

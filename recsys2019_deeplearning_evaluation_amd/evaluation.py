@@ -220,6 +220,8 @@ class EvaluatorHoldout_MI355X(N.Handle):
             self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
         elif isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
+        elif isinstance(rec, GpuSimilarityScoringMixin) and rec.dense_device_scorable():
+            self._run_fused(rec._get_dense_scorer(), "add_dscorer", rec, block)
         elif isinstance(rec, GpuItemScoreMixin):       # (no n x n_items score buffer bounds a launch: fewer, larger blocks)
             self._run_fused(rec._get_item_scorer(), "add_itemscorer", rec,
                             int(block_size) if block_size else min(self.FUSED_BLOCK, len(self.users_to_evaluate)))
@@ -321,6 +323,8 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
             self._run_fused(rec._get_scorer(), "add_scorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
         elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
             self._run_fused(rec._get_sparse_scorer(), "add_spscorer_candidates", rec, int(block_size) if block_size else self._block_size())
+        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.dense_device_scorable():
+            self._run_fused(rec._get_dense_scorer(), "add_dscorer_candidates", rec, int(block_size) if block_size else self._block_size())
         elif self.candidates_on_device and isinstance(rec, GpuItemScoreMixin):
             self._run_fused(rec._get_item_scorer(), "add_itemscorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
         else:

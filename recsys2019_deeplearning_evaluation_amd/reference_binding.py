@@ -20,7 +20,8 @@ recommenders and ItemKNNCustomSimilarityRecommender to the namespace.
 
 `bind(..., BaseRecommender=...)` (`Base.BaseRecommender`) adds TopPop, GlobalEffects and Random.
 
-`device_scoring=False` leaves `recommend()` to the reference's own host implementation (Base/BaseRecommender.py:131).
+`device_scoring=False` leaves `recommend()` to the reference's own host implementation (Base/BaseRecommender.py:131);
+`EASE_R_MI355X_Recommender(..., dense_scoring="device")` then raises ValueError: the dense scorer lives in the scoring mixin.
 """
 from types import SimpleNamespace
 

@@ -197,19 +197,99 @@ class MI355XSparseScorer(_Scorer):
         self._create(A.shape[0], A.shape[1], B.shape[1], *[N.ptr(a) for a in arrs])
 
 
+class MI355XDenseScorer(_Scorer):
+    """scores[u] = A[u, :] . B for a sparse A (CSR, n_users x n_mid) and a DENSE float32 B (n_mid x n_items): an item-similarity model
+    whose W_sparse is an ndarray (A = URM_train, B = W_sparse; BaseSimilarityMatrixRecommender.py:73-92), filtered and ranked on the
+    device like MI355XScorer.  Every score is bit for bit what SciPy's `A[users] @ B` gives: the stored cells of a row of A are summed
+    in their storage order (A's indices are used as given, never sorted), product rounded before the add.  `B` is the array, or
+    its shape `(n_mid, n_items)` for zero weights that `update` / `set_weights_from` fill later."""
+    _PREFIX = "mi355rec_dscorer"
+
+    def __init__(self, A, B, URM_seen):
+        if not sps.isspmatrix_csr(A):
+            A = sps.csr_matrix(A)
+        seen = URM_seen.tocsr()
+        weights = None if isinstance(B, tuple) else self._weights(B, None)
+        n_mid, n_items = B if weights is None else weights.shape
+        assert A.shape[1] == n_mid and seen.shape == (A.shape[0], n_items)
+        self.n_users, self.n_mid, self.n_items = A.shape[0], int(n_mid), int(n_items)
+        arrs = [N.as_i32(A.indptr), N.as_i32(A.indices), N.as_f32(A.data), weights, N.as_i32(seen.indptr), N.as_i32(seen.indices)]
+        self._create(self.n_users, self.n_mid, self.n_items, *[N.ptr(a) for a in arrs])
+
+    @staticmethod
+    def _weights(B, shape):
+        B = N.as_f32(B)
+        if B.ndim != 2 or (shape is not None and B.shape != shape):
+            raise ValueError("the weights must be a 2-d array{}, got {!r}".format("" if shape is None else " of shape %r" % (shape,), B.shape))
+        return B
+
+    def update(self, B):
+        """New weights of the same shape (a second fit); nothing is reallocated."""
+        B = self._weights(B, (self.n_mid, self.n_items))
+        self._call("update", N.ptr(B))
+
+    def set_weights_from(self, ease):
+        """B <- the weights of an `MI355XEase` handle after invert(), device to device: the values `ease.get_dense()` downloads."""
+        if not ease._h:
+            raise ValueError("the EASE handle is closed")
+        self._call("set_from_ease", ease._h)
+
+
 class GpuSimilarityScoringMixin(_ScoringMixin):
     """recommend() for BaseItemSimilarityMatrixRecommender / BaseUserSimilarityMatrixRecommender subclasses, served by
     MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  The scorer is rebuilt whenever W_sparse or
-    URM_train is replaced (fit, early-stopping validation)."""
+    URM_train is replaced (fit, early-stopping validation).
+
+    An item-based model whose W_sparse is a dense ndarray is served by MI355XDenseScorer when the class (or the object) sets
+    `dense_scoring = "device"`; with the default "host" it is scored by the base class on the host, as before.  The dense scorer has a
+    cache of its own under the same rules: strong references, identity plus `_fingerprint` of W (other weights of the same shape
+    are an update), a new scorer when URM_train is replaced."""
     _SCORER_USER_BASED = False
     _sp_scorer = None
     _sp_scorer_src = None
     _SCORER_ATTRS = ("_sp_scorer", "_sp_scorer_src")
+    dense_scoring = "host"
+    _dense_scorer = None
+    _dense_scorer_src = None
 
     def device_scorable(self):
         """False while W_sparse is a dense array (EASE_R with topK=None keeps the reference's ndarray): the sparse scorer takes a CSR, so
-        such a model is scored by the base class on the host -- its own recommend() and the device evaluators' lists path."""
+        such a model is scored by the base class on the host -- its own recommend() and the device evaluators' lists path -- unless
+        `dense_device_scorable()`."""
         return not isinstance(getattr(self, "W_sparse", None), np.ndarray)
+
+    def dense_device_scorable(self):
+        """True when W_sparse is a dense array and `dense_scoring` is "device": recommend() and the device evaluators go through
+        MI355XDenseScorer."""
+        return self.dense_scoring == "device" and not self._SCORER_USER_BASED and isinstance(getattr(self, "W_sparse", None), np.ndarray)
+
+    def _get_dense_scorer(self, weights_from=None):
+        """The dense scorer for the current W_sparse and URM_train.  `weights_from`: an MI355XEase handle that holds W_sparse's values on
+        the device -- they are copied from there instead of being uploaded from the host array."""
+        W = self.W_sparse
+        print_now = _fingerprint(W)
+        old = self._dense_scorer_src
+        scorer = self._dense_scorer
+        fresh = scorer is None or old["urm"] is not self.URM_train or (scorer.n_mid, scorer.n_items) != W.shape
+        if fresh:
+            if scorer is not None:
+                scorer.close()
+                self._dense_scorer = None
+            scorer = MI355XDenseScorer(self.URM_train, W.shape if weights_from is not None else W, self.URM_train)
+            self._dense_scorer = scorer
+        if weights_from is not None:
+            scorer.set_weights_from(weights_from)
+        elif not fresh and (old["W"] is not W or old["print"] != print_now):
+            scorer.update(W)
+        self._dense_scorer_src = {"W": W, "urm": self.URM_train, "print": print_now}
+        return scorer
+
+    def invalidate_scorer(self):
+        super().invalidate_scorer()
+        self._dense_scorer_src = None
+        if self._dense_scorer is not None:
+            self._dense_scorer.close()
+            self._dense_scorer = None
 
     def _get_sparse_scorer(self):
         # strong references + identity (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of
@@ -226,7 +306,7 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
         return self._sp_scorer
 
     def _scorer_for(self, users):
-        return self._get_sparse_scorer()
+        return self._get_dense_scorer() if self.dense_device_scorable() else self._get_sparse_scorer()
 
 
 class MI355XItemScorer(_Scorer):
