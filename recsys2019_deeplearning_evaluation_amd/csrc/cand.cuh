@@ -76,49 +76,5 @@ inline CandParams cand_params(ScorerHandle *h, const int *users, int cutoff, int
     return c;
 }
 
-
-// (buffers only grow after the stream has drained, as in scorer_enqueue)
-inline void grow_ranked(ScorerHandle *h, size_t cells) {
-    if (h->ranked.count < cells) {
-        MI_HIP(hipStreamSynchronize(h->stream));
-        h->ranked.alloc(cells);
-    }
-}
-
-// The body of mi355rec_*scorer_recommend_candidates: row r of the candidate CSR belongs to
-// user_ids[r]; user ids, the rows and the item mask go up, `enqueue` ranks, the lists come down.
-template <class H, class Enqueue, class BadUser>
-void recommend_candidates(H *h, const int32_t *user_ids, int n, const int32_t *cand_indptr, const int32_t *cand_indices, int cutoff,
-                          int remove_seen, const uint8_t *item_allowed, int32_t *ranked, Enqueue enqueue, BadUser bad_user) {
-    MI_REQUIRE(h && user_ids && cand_indptr && ranked, "NULL argument");
-    MI_REQUIRE(n > 0, "empty user batch");
-    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-    for (int i = 0; i < n; ++i)
-        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) bad_user(user_ids[i]);
-    const int longest = check_candidate_rows(cand_indptr, cand_indices, n, h->n_items);
-    check_candidate_cutoff(cutoff);     // (before anything is uploaded; the enqueue functions check for every caller)
-    ensure_device();
-    hipStream_t s = h->stream;
-    const size_t nnz = (size_t)cand_indptr[n];
-    if (h->users.count < (size_t)n || h->cand_ptr.count < (size_t)n + 1 || h->cand_idx.count < std::max<size_t>(nnz, 1)) {
-        MI_HIP(hipStreamSynchronize(s));
-        if (h->users.count < (size_t)n) h->users.alloc(n);
-        if (h->cand_ptr.count < (size_t)n + 1) h->cand_ptr.alloc((size_t)n + 1);
-        if (h->cand_idx.count < std::max<size_t>(nnz, 1)) h->cand_idx.alloc(std::max<size_t>(nnz, 1));
-    }
-    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-    MI_HIP(hipMemcpyAsync(h->cand_ptr.ptr, cand_indptr, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
-    if (nnz) MI_HIP(hipMemcpyAsync(h->cand_idx.ptr, cand_indices, sizeof(int) * nnz, hipMemcpyHostToDevice, s));
-    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-    enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr,
-            CandidateRows{h->cand_ptr.ptr, h->cand_idx.ptr, false, longest});
-    h->ranked.download(ranked, (size_t)n * cutoff, s);
-    MI_HIP(hipStreamSynchronize(s));
-    h->stats = mi355rec_stats{};
-    h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms();      // the candidate kernel(s): there is no GEMM to tell apart
-    h->stats.n_launches = h->stats.n_timed = 1;
-    h->stats.n_units = n;
-}
-
 }  // namespace
 }  // namespace mi355rec

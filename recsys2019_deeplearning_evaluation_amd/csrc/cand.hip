@@ -176,85 +176,104 @@ int check_candidate_rows(const int32_t *indptr, const int32_t *indices, int n_ro
     return longest;
 }
 
-Ranking scorer_enqueue_candidates(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                                  const CandidateRows &rows) {
+void recommend_candidates(ScorerHandle *h, const int32_t *user_ids, int n, const int32_t *cand_indptr, const int32_t *cand_indices,
+                          int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked) {
+    MI_REQUIRE(h && user_ids && cand_indptr && ranked, "NULL argument");
+    MI_REQUIRE(n > 0, "empty user batch");
+    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
+    for (int i = 0; i < n; ++i)
+        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) h->bad_user(user_ids[i]);
+    const int longest = check_candidate_rows(cand_indptr, cand_indices, n, h->n_items);
+    check_candidate_cutoff(cutoff);     // (before anything is uploaded; enqueue_candidates checks for every caller)
+    ensure_device();
     hipStream_t s = h->stream;
-    check_candidate_cutoff(cutoff);
-    grow_ranked(h, (size_t)n * cutoff);
-    CandScoreParams p{};
-    p.c = cand_params(h, users, cutoff, remove_seen, allowed, rows);
-    p.k = h->k; p.use_bias = h->use_bias;
-    p.vec = (h->k & 3) == 0;
-    const int units = p.vec ? h->k >> 2 : h->k;
-    p.lanes = 1;
-    while (p.lanes < 64 && p.lanes < units) p.lanes <<= 1;
-    p.cand_pad = cand_buffer_entries(rows.longest);
-    p.U = h->U.ptr; p.V = h->V.ptr; p.bu = h->bu.ptr; p.bi = h->bi.ptr; p.mu = h->mu;
-    const size_t lds = (size_t)p.cand_pad * 8 + (size_t)((h->k + 3) & ~3) * 4;
-    if (lds + 1024 > 160 * 1024) fail(MI355REC_E_UNSUPPORTED, "%d factors do not fit LDS next to the candidate buffer", h->k);
-    auto k = cand_score_rank_kernel<CAND_THREADS>;
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipExtLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
-    MI_HIP(hipGetLastError());
-    return Ranking{h->ranked.ptr, s};
-}
-
-Ranking spscorer_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
-                                    const unsigned char *allowed, const CandidateRows &rows) {
-    hipStream_t s = h->stream;
-    check_candidate_cutoff(cutoff);
-    const bool in_lds = score_row_fits_lds(h->n_items, cutoff);
-    grow_ranked(h, (size_t)n * cutoff);
-    if (!in_lds && h->scores.count < (size_t)n * h->n_items) {
+    const size_t nnz = (size_t)cand_indptr[n];
+    if (h->users.count < (size_t)n || h->cand_ptr.count < (size_t)n + 1 || h->cand_idx.count < std::max<size_t>(nnz, 1)) {
         MI_HIP(hipStreamSynchronize(s));
-        h->scores.alloc((size_t)n * h->n_items);
+        if (h->users.count < (size_t)n) h->users.alloc(n);
+        if (h->cand_ptr.count < (size_t)n + 1) h->cand_ptr.alloc((size_t)n + 1);
+        if (h->cand_idx.count < std::max<size_t>(nnz, 1)) h->cand_idx.alloc(std::max<size_t>(nnz, 1));
     }
-    const CandParams c = cand_params(h, users, cutoff, remove_seen, allowed, rows);
-    h->timer.start(s);
-    if (in_lds) {
-        SpCandParams p{};
-        p.c = c; p.n_pad = (h->n_items + 3) & ~3;
-        p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
-        p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
-        const size_t lds = (size_t)p.n_pad * 4 + (size_t)AUX_WORDS * 4;
-        auto k = spscore_cand_kernel<1024>;
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k, dim3(n), dim3(1024), lds, s, p);
-    } else {
-        spscorer_enqueue_wide_rows(h, users, n);
-        const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
-        auto k = cand_gather_rank_kernel<CAND_THREADS>;
-        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), lds, s, c, (const float *)h->scores.ptr, h->n_items);
-    }
-    MI_HIP(hipGetLastError());
-    h->timer.stop(s);
-    return Ranking{h->ranked.ptr, s};
+    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    MI_HIP(hipMemcpyAsync(h->cand_ptr.ptr, cand_indptr, sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+    if (nnz) MI_HIP(hipMemcpyAsync(h->cand_idx.ptr, cand_indices, sizeof(int) * nnz, hipMemcpyHostToDevice, s));
+    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
+    h->enqueue_candidates(h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr,
+                          CandidateRows{h->cand_ptr.ptr, h->cand_idx.ptr, false, longest});
+    h->ranked.download(ranked, (size_t)n * cutoff, s);
+    MI_HIP(hipStreamSynchronize(s));
+    h->stats = mi355rec_stats{};
+    h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms();      // the candidate kernel(s): there is no GEMM to tell apart
+    h->stats.n_launches = h->stats.n_timed = 1;
+    h->stats.n_units = n;
 }
 
 }  // namespace mi355rec
 
 using namespace mi355rec;
 
+Ranking mi355rec_scorer::enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                            const CandidateRows &rows) {
+    hipStream_t s = stream;
+    check_candidate_cutoff(cutoff);
+    reserve((size_t)n * cutoff, 0, 0);
+    CandScoreParams p{};
+    p.c = cand_params(this, users, cutoff, remove_seen, allowed, rows);
+    p.k = k; p.use_bias = use_bias;
+    p.vec = (k & 3) == 0;
+    const int units = p.vec ? k >> 2 : k;
+    p.lanes = 1;
+    while (p.lanes < 64 && p.lanes < units) p.lanes <<= 1;
+    p.cand_pad = cand_buffer_entries(rows.longest);
+    p.U = U.ptr; p.V = V.ptr; p.bu = bu.ptr; p.bi = bi.ptr; p.mu = mu;
+    const size_t lds = (size_t)p.cand_pad * 8 + (size_t)((k + 3) & ~3) * 4;
+    if (lds + 1024 > 160 * 1024) fail(MI355REC_E_UNSUPPORTED, "%d factors do not fit LDS next to the candidate buffer", k);
+    auto kernel = cand_score_rank_kernel<CAND_THREADS>;
+    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipExtLaunchKernelGGL(kernel, dim3(n), dim3(CAND_THREADS), (unsigned)lds, s, timer.t0, timer.t1, 0, p);
+    MI_HIP(hipGetLastError());
+    return Ranking{ranked.ptr, s};
+}
+
+Ranking mi355rec_spscorer::enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                              const CandidateRows &rows) {
+    hipStream_t s = stream;
+    check_candidate_cutoff(cutoff);
+    const bool in_lds = score_row_fits_lds(n_items, cutoff);
+    reserve((size_t)n * cutoff, in_lds ? 0 : (size_t)n * n_items, 0);
+    const CandParams c = cand_params(this, users, cutoff, remove_seen, allowed, rows);
+    timer.start(s);
+    if (in_lds) {
+        SpCandParams p{};
+        p.c = c; p.n_pad = (n_items + 3) & ~3;
+        p.a_ptr = a_ptr.ptr; p.a_idx = a_idx.ptr; p.a_val = a_val.ptr;
+        p.b_ptr = b_ptr.ptr; p.b_idx = b_idx.ptr; p.b_val = b_val.ptr;
+        const size_t lds = (size_t)p.n_pad * 4 + (size_t)AUX_WORDS * 4;
+        auto k = spscore_cand_kernel<1024>;
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(n), dim3(1024), lds, s, p);
+    } else {
+        spscorer_enqueue_wide_rows(this, users, n);
+        const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
+        auto k = cand_gather_rank_kernel<CAND_THREADS>;
+        MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), lds, s, c, (const float *)scores.ptr, n_items);
+    }
+    MI_HIP(hipGetLastError());
+    timer.stop(s);
+    return Ranking{ranked.ptr, s};
+}
+
 extern "C" int mi355rec_scorer_recommend_candidates(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                                     const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
                                                     const uint8_t *item_allowed, int32_t *ranked) {
-    return guarded([&] {
-        recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked, scorer_enqueue_candidates,
-                             [&](int u) {
-                                 fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d",
-                                      h->n_users, u);
-                             });
-    });
+    return guarded([&] { recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked); });
 }
 
 extern "C" int mi355rec_spscorer_recommend_candidates(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                                       const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
                                                       const uint8_t *item_allowed, int32_t *ranked) {
-    return guarded([&] {
-        recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked, spscorer_enqueue_candidates,
-                             [](int u) { fail(MI355REC_E_INVALID, "user id %d out of range", u); });
-    });
+    return guarded([&] { recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked); });
 }
 
 extern "C" int mi355rec_scorer_score_capacity(mi355rec_scorer_t h, int64_t *cells) {

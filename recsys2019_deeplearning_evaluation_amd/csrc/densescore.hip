@@ -172,47 +172,56 @@ int unroll_depth() {
 
 }  // namespace
 
-// The score + rank half of mi355rec_dscorer_recommend (see scorer_enqueue).  `timer`: the scoring dispatch; `call_timer`: scoring +
-// ranking.
-Ranking dscorer_enqueue(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                        bool keep_scores) {
-    hipStream_t s = h->stream;
-    const int tiles = div_up(h->n_items, DSCORE_TILE);
-    if (tiles > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d items: at most %d", h->n_items, 65535 * DSCORE_TILE);
-    grow_score_rows(h, n, cutoff);
-    h->call_timer.start(s);
-    DScoreParams p{};
-    p.n_out = h->n_items; p.ldb = h->ldb;
-    p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr; p.B = h->B.ptr;
-    p.users = users; p.scores = h->scores.ptr;
-    if (h->unroll == 4) hipExtLaunchKernelGGL(dscore_rows_kernel<4>, dim3(n, tiles), dim3(DSCORE_THREADS), 0, s, h->timer.t0, h->timer.t1, 0, p);
-    else hipExtLaunchKernelGGL(dscore_rows_kernel<8>, dim3(n, tiles), dim3(DSCORE_THREADS), 0, s, h->timer.t0, h->timer.t1, 0, p);
-    MI_HIP(hipGetLastError());
-    rank_rows_enqueue(h, users, n, cutoff, remove_seen, allowed, keep_scores);
-    h->call_timer.stop(s);
-    return Ranking{h->ranked.ptr, s};
-}
-
-Ranking dscorer_enqueue_candidates(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                                   const CandidateRows &rows) {
-    hipStream_t s = h->stream;
-    check_candidate_cutoff(cutoff);
-    grow_ranked(h, (size_t)n * cutoff);
-    DCandParams p{};
-    p.c = cand_params(h, users, cutoff, remove_seen, allowed, rows);
-    p.ldb = h->ldb;
-    p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr; p.B = h->B.ptr;
-    const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
-    auto k = dscore_cand_kernel<CAND_THREADS>;
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipExtLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
-    MI_HIP(hipGetLastError());
-    return Ranking{h->ranked.ptr, s};
-}
-
 }  // namespace mi355rec
 
 using namespace mi355rec;
+
+// The score + rank half of mi355rec_dscorer_recommend (see mi355rec_scorer::enqueue).  `timer`: the scoring dispatch; `call_timer`:
+// scoring + ranking.
+Ranking mi355rec_dscorer::enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) {
+    hipStream_t s = stream;
+    const int tiles = div_up(n_items, DSCORE_TILE);
+    if (tiles > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d items: at most %d", n_items, 65535 * DSCORE_TILE);
+    const size_t cells = (size_t)n * n_items;
+    reserve((size_t)n * cutoff, cells, score_row_fits_lds(n_items, cutoff) ? 0 : cells);
+    call_timer.start(s);
+    DScoreParams p{};
+    p.n_out = n_items; p.ldb = ldb;
+    p.a_ptr = a_ptr.ptr; p.a_idx = a_idx.ptr; p.a_val = a_val.ptr; p.B = B.ptr;
+    p.users = users; p.scores = scores.ptr;
+    if (unroll == 4) hipExtLaunchKernelGGL(dscore_rows_kernel<4>, dim3(n, tiles), dim3(DSCORE_THREADS), 0, s, timer.t0, timer.t1, 0, p);
+    else hipExtLaunchKernelGGL(dscore_rows_kernel<8>, dim3(n, tiles), dim3(DSCORE_THREADS), 0, s, timer.t0, timer.t1, 0, p);
+    MI_HIP(hipGetLastError());
+    rank_rows_enqueue(this, users, n, cutoff, remove_seen, allowed, keep_scores);
+    call_timer.stop(s);
+    return Ranking{ranked.ptr, s};
+}
+
+Ranking mi355rec_dscorer::enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                             const CandidateRows &rows) {
+    hipStream_t s = stream;
+    check_candidate_cutoff(cutoff);
+    reserve((size_t)n * cutoff, 0, 0);
+    DCandParams p{};
+    p.c = cand_params(this, users, cutoff, remove_seen, allowed, rows);
+    p.ldb = ldb;
+    p.a_ptr = a_ptr.ptr; p.a_idx = a_idx.ptr; p.a_val = a_val.ptr; p.B = B.ptr;
+    const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
+    auto k = dscore_cand_kernel<CAND_THREADS>;
+    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipExtLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), (unsigned)lds, s, timer.t0, timer.t1, 0, p);
+    MI_HIP(hipGetLastError());
+    return Ranking{ranked.ptr, s};
+}
+
+void mi355rec_dscorer::fill_recommend_stats(const int32_t *user_ids, int n) {
+    double nnz = 0;                                     // stored cells of the batch's profiles: each one streams a row of B
+    for (int i = 0; i < n; ++i) nnz += a_ptr_host[user_ids[i] + 1] - a_ptr_host[user_ids[i]];
+    stats.call_ms = call_timer.elapsed_ms();
+    stats.kernel_ms = timer.elapsed_ms();
+    stats.algorithmic_flops = 2.0 * nnz * n_items;
+    stats.algorithmic_bytes = 4.0 * nnz * n_items;
+}
 
 extern "C" int mi355rec_dscorer_create(mi355rec_dscorer_t *out, int32_t n_users, int32_t n_mid, int32_t n_out, const int32_t *a_indptr,
                                        const int32_t *a_indices, const float *a_data, const float *B, const int32_t *seen_indptr,
@@ -289,43 +298,13 @@ extern "C" int mi355rec_dscorer_set_from_ease(mi355rec_dscorer_t h, mi355rec_eas
 
 extern "C" int mi355rec_dscorer_recommend(mi355rec_dscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
                                           const uint8_t *item_allowed, int32_t *ranked, float *scores) {
-    return guarded([&] {
-        MI_REQUIRE(h && user_ids && ranked, "NULL argument");
-        MI_REQUIRE(n > 0, "empty user batch");
-        MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-        for (int i = 0; i < n; ++i)
-            if (user_ids[i] < 0 || user_ids[i] >= h->n_users) fail(MI355REC_E_INVALID, "user id %d out of range", user_ids[i]);
-        ensure_device();
-        hipStream_t s = h->stream;
-        if (h->users.count < (size_t)n) {
-            MI_HIP(hipStreamSynchronize(s));
-            h->users.alloc(n);
-        }
-        MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-        dscorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
-        h->ranked.download(ranked, (size_t)n * cutoff, s);
-        if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
-        MI_HIP(hipStreamSynchronize(s));
-        double nnz = 0;                                 // stored cells of the batch's profiles: each one streams a row of B
-        for (int i = 0; i < n; ++i) nnz += h->a_ptr_host[user_ids[i] + 1] - h->a_ptr_host[user_ids[i]];
-        h->stats = mi355rec_stats{};
-        h->stats.call_ms = h->call_timer.elapsed_ms();
-        h->stats.kernel_ms = h->timer.elapsed_ms();
-        h->stats.n_launches = h->stats.n_timed = 1;
-        h->stats.n_units = n;
-        h->stats.algorithmic_flops = 2.0 * nnz * h->n_items;
-        h->stats.algorithmic_bytes = 4.0 * nnz * h->n_items;
-    });
+    return guarded([&] { recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores); });
 }
 
 extern "C" int mi355rec_dscorer_recommend_candidates(mi355rec_dscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                                      const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
                                                      const uint8_t *item_allowed, int32_t *ranked) {
-    return guarded([&] {
-        recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked, dscorer_enqueue_candidates,
-                             [](int u) { fail(MI355REC_E_INVALID, "user id %d out of range", u); });
-    });
+    return guarded([&] { recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked); });
 }
 
 extern "C" int mi355rec_dscorer_get_stats(mi355rec_dscorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }

@@ -9,10 +9,10 @@
 //                       [user][cutoff][value]; every list entry adds 1 to counts[b][item] (b = the smallest cutoff that holds it).
 //   eval_sum_kernel     each (cutoff, value) column summed over all users in a fixed order (no floating-point atomics).
 //   eval_counts_kernel  counts[b] -> counts of every cutoff: a running sum over b.
-// The lists come either from a device scorer (score.hip: scorer_enqueue / spscorer_enqueue, the kernel runs on the scorer's
-// stream and reads its `ranked` buffer in place) or from the host (the lists path).  For the reference's EvaluatorNegativeItemSample
-// (Evaluator.py:455-539) the scorers rank each user's candidate row only (cand.hip: *_enqueue_candidates; the rows are uploaded once
-// by mi355rec_eval_set_candidates); the metric kernel and finish are the same.
+// The lists come either from a device scorer (score.h: ScorerHandle::enqueue, the kernel runs on the scorer's stream and reads its
+// `ranked` buffer in place) or from the host (the lists path).  For the reference's EvaluatorNegativeItemSample (Evaluator.py:455-539)
+// the scorers rank each user's candidate row only (ScorerHandle::enqueue_candidates; the rows are uploaded once by
+// mi355rec_eval_set_candidates); the metric kernel and finish are the same.
 #include "common.h"
 #include "score.h"
 #include "itemscore.h"
@@ -274,8 +274,9 @@ const unsigned char *device_mask(mi355rec_eval *h, const uint8_t *allowed) {
     return h->allowed.ptr;
 }
 
-template <class Scorer, class Enqueue>
-void add_from_scorer(mi355rec_eval *h, Scorer *sc, int first, int n, int remove_seen, const uint8_t *allowed, Enqueue enqueue) {
+// A block of users through a scorer: its lists stay in HBM.  `rows`: rank the candidate rows only (negative-sample evaluation).
+void add_from_scorer(mi355rec_eval *h, ScorerHandle *sc, int first, int n, int remove_seen, const uint8_t *allowed,
+                     const CandidateRows *rows = nullptr) {
     MI_REQUIRE(h && sc, "NULL argument");
     check_block(h, first, n);
     const int su = sc->n_users, si = sc->n_items;
@@ -286,9 +287,19 @@ void add_from_scorer(mi355rec_eval *h, Scorer *sc, int first, int n, int remove_
     ensure_device();
     const unsigned char *mask = device_mask(h, allowed);
     MI_HIP(hipStreamWaitEvent(sc->stream, h->done, 0)); // (begin's zeroing, a lists-path block on the evaluator's stream)
-    const Ranking r = enqueue(sc, h->users.ptr + first, n, h->width, remove_seen, mask, false);
+    const int *users = h->users.ptr + first;
+    const Ranking r = rows ? sc->enqueue_candidates(users, n, h->width, remove_seen, mask, *rows)
+                           : sc->enqueue(users, n, h->width, remove_seen, mask, false);
     launch_metrics(h, r.stream, r.ranked, first, n);    // behind the ranking, on the scorer's stream: the next block's ranking
 }                                                       // cannot overwrite `ranked` before this kernel has read it
+
+// Negative-sample evaluation (Evaluator.py:455-539, EvaluatorNegativeItemSample): every user ranks the candidates of its row only.
+void add_from_scorer_candidates(mi355rec_eval *h, ScorerHandle *sc, int first, int n, int remove_seen, const uint8_t *allowed) {
+    MI_REQUIRE(h, "NULL argument");
+    MI_REQUIRE(h->cand_longest >= 0, "mi355rec_eval_set_candidates has not been called");
+    const CandidateRows rows{h->cand_ptr.ptr, h->cand_idx.ptr, true, h->cand_longest};
+    add_from_scorer(h, sc, first, n, remove_seen, allowed, &rows);
+}
 }  // namespace
 
 extern "C" int mi355rec_eval_create(mi355rec_eval_t *out, int32_t n_users, int32_t n_items, const int32_t *test_indptr,
@@ -398,27 +409,27 @@ extern "C" int mi355rec_eval_add_lists(mi355rec_eval_t h, int32_t first, int32_t
     });
 }
 
+// One entry point per scorer type: the typed pointer of the C header is what keeps a wrong handle out.
 extern "C" int mi355rec_eval_add_scorer(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                         const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, scorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_spscorer(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                           const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_itemscorer(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                             const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_dscorer(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n, int32_t remove_seen,
                                          const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed, dscorer_enqueue); });
+    return guarded([&] { add_from_scorer(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
-// Negative-sample evaluation (Evaluator.py:455-539, EvaluatorNegativeItemSample): every user ranks the candidates of its row only.
 extern "C" int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *indptr, const int32_t *indices) {
     return guarded([&] {
         MI_REQUIRE(h && indptr, "NULL argument");
@@ -437,37 +448,24 @@ extern "C" int mi355rec_eval_set_candidates(mi355rec_eval_t h, const int32_t *in
     });
 }
 
-namespace {
-template <class Scorer, class Enqueue>
-void add_from_scorer_candidates(mi355rec_eval *h, Scorer *sc, int first, int n, int remove_seen, const uint8_t *allowed, Enqueue enqueue) {
-    MI_REQUIRE(h, "NULL argument");
-    MI_REQUIRE(h->cand_longest >= 0, "mi355rec_eval_set_candidates has not been called");
-    const CandidateRows rows{h->cand_ptr.ptr, h->cand_idx.ptr, true, h->cand_longest};
-    add_from_scorer(h, sc, first, n, remove_seen, allowed,
-                    [&](Scorer *scorer, const int *users, int count, int cutoff, int seen, const unsigned char *mask, bool) {
-                        return enqueue(scorer, users, count, cutoff, seen, mask, rows);
-                    });
-}
-}  // namespace
-
 extern "C" int mi355rec_eval_add_scorer_candidates(mi355rec_eval_t h, mi355rec_scorer_t scorer, int32_t first, int32_t n,
                                                    int32_t remove_seen, const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, scorer_enqueue_candidates); });
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_spscorer_candidates(mi355rec_eval_t h, mi355rec_spscorer_t scorer, int32_t first, int32_t n,
                                                      int32_t remove_seen, const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, spscorer_enqueue_candidates); });
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_itemscorer_candidates(mi355rec_eval_t h, mi355rec_itemscorer_t scorer, int32_t first, int32_t n,
                                                        int32_t remove_seen, const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, itemscorer_enqueue_candidates); });
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_add_dscorer_candidates(mi355rec_eval_t h, mi355rec_dscorer_t scorer, int32_t first, int32_t n,
                                                     int32_t remove_seen, const uint8_t *item_allowed) {
-    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed, dscorer_enqueue_candidates); });
+    return guarded([&] { add_from_scorer_candidates(h, scorer, first, n, remove_seen, item_allowed); });
 }
 
 extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts) {

@@ -218,70 +218,61 @@ void create(mi355rec_itemscorer_t *out, int n_users, int n_items, const float *i
     *out = h.release();
 }
 
-// (buffers only grow after the stream has drained, as in scorer_enqueue)
-void grow(mi355rec_itemscorer *h, size_t ranked_cells, size_t score_cells) {
-    if (h->ranked.count < ranked_cells || h->scores.count < score_cells) {
-        MI_HIP(hipStreamSynchronize(h->stream));
-        if (h->ranked.count < ranked_cells) h->ranked.alloc(ranked_cells);
-        if (h->scores.count < score_cells) h->scores.alloc(score_cells);
-    }
-}
-
 }  // namespace
-
-Ranking itemscorer_enqueue(mi355rec_itemscorer *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                           bool keep_scores) {
-    hipStream_t s = h->stream;
-    if (keep_scores && n > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d users in one call: at most 65535", n);
-    grow(h, (size_t)n * cutoff, keep_scores ? (size_t)n * h->n_items : 0);
-    h->timer.start(s);
-    ItemRankParams p{};
-    p.cutoff = cutoff; p.remove_seen = remove_seen;
-    p.order = h->order.ptr; p.rank_of = h->rank_of.ptr; p.length = h->length.ptr;
-    if (allowed) {                              // the order without the excluded items, and its inverse
-        if (h->n_order) {
-            size_t bytes = h->tmp.count;
-            MI_HIP(rocprim::select(h->tmp.ptr, bytes, h->order.ptr, h->m_order.ptr, h->m_length.ptr, (size_t)h->n_order, AllowedItem{allowed}, s));
-        } else {
-            MI_HIP(hipMemsetAsync(h->m_length.ptr, 0, sizeof(int), s));
-        }
-        scatter_ranks(s, h->m_order.ptr, h->m_length.ptr, h->n_order, h->n_items, h->m_rank_of.ptr);
-        p.order = h->m_order.ptr; p.rank_of = h->m_rank_of.ptr; p.length = h->m_length.ptr;
-    }
-    p.users = users; p.seen_ptr = h->seen_ptr.ptr; p.seen_idx = h->seen_idx.ptr;
-    p.ranked = h->ranked.ptr;
-    if (h->window_bits == WAVE_WINDOW) hipLaunchKernelGGL(itemscore_rank_kernel<64>, dim3(n), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL(itemscore_rank_kernel<256>, dim3(n), dim3(256), 0, s, p);
-    if (keep_scores) {
-        hipLaunchKernelGGL(itemscore_fill_kernel, dim3(std::min(div_up(h->n_items, 256), 64), n), dim3(256), 0, s, h->vec.ptr, allowed,
-                           h->n_items, h->scores.ptr);
-        if (remove_seen)
-            hipLaunchKernelGGL(itemscore_seen_kernel, dim3(n), dim3(256), 0, s, users, h->seen_ptr.ptr, h->seen_idx.ptr, h->n_items, h->scores.ptr);
-    }
-    MI_HIP(hipGetLastError());
-    h->timer.stop(s);
-    return Ranking{h->ranked.ptr, s};
-}
-
-Ranking itemscorer_enqueue_candidates(mi355rec_itemscorer *h, const int *users, int n, int cutoff, int remove_seen,
-                                      const unsigned char *allowed, const CandidateRows &rows) {
-    hipStream_t s = h->stream;
-    check_candidate_cutoff(cutoff);
-    grow_ranked(h, (size_t)n * cutoff);
-    const CandParams c = cand_params(h, users, cutoff, remove_seen, allowed, rows);
-    const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
-    auto k = itemscore_cand_kernel<CAND_THREADS>;
-    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->timer.start(s);
-    hipLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), lds, s, c, (const float *)h->vec.ptr);
-    MI_HIP(hipGetLastError());
-    h->timer.stop(s);
-    return Ranking{h->ranked.ptr, s};
-}
-
 }  // namespace mi355rec
 
 using namespace mi355rec;
+
+Ranking mi355rec_itemscorer::enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) {
+    hipStream_t s = stream;
+    if (keep_scores && n > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d users in one call: at most 65535", n);
+    reserve((size_t)n * cutoff, keep_scores ? (size_t)n * n_items : 0, 0);
+    timer.start(s);
+    ItemRankParams p{};
+    p.cutoff = cutoff; p.remove_seen = remove_seen;
+    p.order = order.ptr; p.rank_of = rank_of.ptr; p.length = length.ptr;
+    if (allowed) {                              // the order without the excluded items, and its inverse
+        if (n_order) {
+            size_t bytes = tmp.count;
+            MI_HIP(rocprim::select(tmp.ptr, bytes, order.ptr, m_order.ptr, m_length.ptr, (size_t)n_order, AllowedItem{allowed}, s));
+        } else {
+            MI_HIP(hipMemsetAsync(m_length.ptr, 0, sizeof(int), s));
+        }
+        scatter_ranks(s, m_order.ptr, m_length.ptr, n_order, n_items, m_rank_of.ptr);
+        p.order = m_order.ptr; p.rank_of = m_rank_of.ptr; p.length = m_length.ptr;
+    }
+    p.users = users; p.seen_ptr = seen_ptr.ptr; p.seen_idx = seen_idx.ptr;
+    p.ranked = ranked.ptr;
+    if (window_bits == WAVE_WINDOW) hipLaunchKernelGGL(itemscore_rank_kernel<64>, dim3(n), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL(itemscore_rank_kernel<256>, dim3(n), dim3(256), 0, s, p);
+    if (keep_scores) {
+        hipLaunchKernelGGL(itemscore_fill_kernel, dim3(std::min(div_up(n_items, 256), 64), n), dim3(256), 0, s, vec.ptr, allowed, n_items,
+                           scores.ptr);
+        if (remove_seen)
+            hipLaunchKernelGGL(itemscore_seen_kernel, dim3(n), dim3(256), 0, s, users, seen_ptr.ptr, seen_idx.ptr, n_items, scores.ptr);
+    }
+    MI_HIP(hipGetLastError());
+    timer.stop(s);
+    return Ranking{ranked.ptr, s};
+}
+
+Ranking mi355rec_itemscorer::enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                                const CandidateRows &rows) {
+    hipStream_t s = stream;
+    check_candidate_cutoff(cutoff);
+    reserve((size_t)n * cutoff, 0, 0);
+    const CandParams c = cand_params(this, users, cutoff, remove_seen, allowed, rows);
+    const size_t lds = (size_t)cand_buffer_entries(rows.longest) * 8;
+    auto k = itemscore_cand_kernel<CAND_THREADS>;
+    MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    timer.start(s);
+    hipLaunchKernelGGL(k, dim3(n), dim3(CAND_THREADS), lds, s, c, (const float *)vec.ptr);
+    MI_HIP(hipGetLastError());
+    timer.stop(s);
+    return Ranking{ranked.ptr, s};
+}
+
+void mi355rec_itemscorer::fill_recommend_stats(const int32_t *, int) { stats.kernel_ms = stats.call_ms = timer.elapsed_ms(); }
 
 extern "C" int mi355rec_itemscorer_create(mi355rec_itemscorer_t *out, int32_t n_users, int32_t n_items, const float *item_scores,
                                           const int32_t *seen_indptr, const int32_t *seen_indices) {
@@ -304,43 +295,13 @@ extern "C" int mi355rec_itemscorer_update(mi355rec_itemscorer_t h, const float *
 
 extern "C" int mi355rec_itemscorer_recommend(mi355rec_itemscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff, int32_t remove_seen,
                                              const uint8_t *item_allowed, int32_t *ranked, float *scores) {
-    return guarded([&] {
-        MI_REQUIRE(h && user_ids && ranked, "NULL argument");
-        MI_REQUIRE(n > 0, "empty user batch");
-        MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-        for (int i = 0; i < n; ++i)
-            if (user_ids[i] < 0 || user_ids[i] >= h->n_users)
-                fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d", h->n_users,
-                     user_ids[i]);
-        ensure_device();
-        hipStream_t s = h->stream;
-        if (h->users.count < (size_t)n) {
-            MI_HIP(hipStreamSynchronize(s));
-            h->users.alloc(n);
-        }
-        MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-        itemscorer_enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
-        h->ranked.download(ranked, (size_t)n * cutoff, s);
-        if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
-        MI_HIP(hipStreamSynchronize(s));
-        h->stats = mi355rec_stats{};
-        h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms();
-        h->stats.n_launches = h->stats.n_timed = 1;
-        h->stats.n_units = n;
-    });
+    return guarded([&] { recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores); });
 }
 
 extern "C" int mi355rec_itemscorer_recommend_candidates(mi355rec_itemscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                                         const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
                                                         const uint8_t *item_allowed, int32_t *ranked) {
-    return guarded([&] {
-        recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked, itemscorer_enqueue_candidates,
-                             [&](int u) {
-                                 fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d",
-                                      h->n_users, u);
-                             });
-    });
+    return guarded([&] { recommend_candidates(h, user_ids, n, cand_indptr, cand_indices, cutoff, remove_seen, item_allowed, ranked); });
 }
 
 extern "C" int mi355rec_itemscorer_window_bits(mi355rec_itemscorer_t h, int32_t *bits) {

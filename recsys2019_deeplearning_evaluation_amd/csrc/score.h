@@ -1,8 +1,7 @@
-// score.h -- the scorer handles (factor, sparse-similarity and -- densescore.hip -- dense-similarity models) and the "score + rank on
-// the handle's stream" half of mi355rec_scorer_recommend / mi355rec_spscorer_recommend (score.hip) and mi355rec_dscorer_recommend
-// (densescore.hip), shared with the holdout evaluator (eval.hip), whose metric kernel reads the ranked lists
-// where these leave them; and the same for candidate rows (cand.hip: mi355rec_*scorer_recommend_candidates, the negative-sample
-// evaluator).
+// score.h -- the scorer handles (factor, sparse-similarity and -- densescore.hip -- dense-similarity models; itemscore.h adds the shared
+// item vector) and their one interface, ScorerHandle: `enqueue` and `enqueue_candidates` put "score + rank" on the handle's stream and
+// leave the lists in `ranked`.  The public mi355rec_*scorer_recommend[_candidates] (recommend / recommend_candidates below) and the
+// holdout evaluators (eval.hip: add_from_scorer, whose metric kernel reads the lists where they stand) are written against it.
 #pragma once
 
 #include "common.h"
@@ -22,69 +21,11 @@ struct WideRanker {
               const unsigned char *allowed, int remove_seen, int *ranked);
 };
 
-// what the two scorers share: mi355rec_*scorer_recommend and the evaluator's add_from_scorer are written against these members
-struct ScorerHandle : Handle {
-    WideRanker wide;
-    int n_users = 0, n_items = 0;       // rows that can be asked for, width of a score row
-    DeviceBuffer<int> seen_ptr, seen_idx, users, ranked;
-    DeviceBuffer<int> cand_ptr, cand_idx;   // the candidate rows of the last mi355rec_*scorer_recommend_candidates
-    DeviceBuffer<float> scores;
-    DeviceBuffer<unsigned char> allowed;
-};
-
-}  // namespace mi355rec
-
-struct mi355rec_scorer : mi355rec::ScorerHandle {    // `timer`: the GEMM dispatch; `call_timer`: GEMM + ranking
-    int k = 0, use_bias = 0;
-    float mu = 0.f;
-    mi355rec::DeviceBuffer<float> U, V, bu, bi;
-
-    ~mi355rec_scorer() { shutdown(); }
-};
-
-struct mi355rec_spscorer : mi355rec::ScorerHandle {  // `timer`: the scoring dispatch
-    int n_mid = 0;
-    mi355rec::DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx;
-    mi355rec::DeviceBuffer<float> a_val, b_val;
-    double nnz_a = 0, nnz_b = 0;
-
-    ~mi355rec_spscorer() { shutdown(); }
-};
-
-struct mi355rec_dscorer : mi355rec::ScorerHandle {   // densescore.hip.  `timer`: the scoring dispatch; `call_timer`: scoring + ranking
-    int n_mid = 0, unroll = 0;
-    int64_t ldb = 0;                                 // floats between two rows of B (n_items rounded up to 4)
-    mi355rec::DeviceBuffer<int> a_ptr, a_idx;        // A as stored: the order of a row's cells is the order of the sum
-    mi355rec::DeviceBuffer<float> a_val, B;
-    std::vector<int> a_ptr_host;                     // (the stats count the stored cells of a batch's profiles)
-
-    ~mi355rec_dscorer() { shutdown(); }
-};
-
-namespace mi355rec {
-
 struct Ranking {
     const int *ranked;      // [n][cutoff] on the device, -1 padded; valid until the next enqueue on the same handle
     hipStream_t stream;     // the handle's stream: the work above is queued there, nothing has been waited for
 };
 
-// users: n device user ids; allowed: nullable device mask of n_items bytes; keep_scores: leave the filtered score rows in the
-// handle's score buffer (the public functions' return_scores).
-Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                       bool keep_scores);
-Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                         bool keep_scores);
-Ranking dscorer_enqueue(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                        bool keep_scores);
-// What a scorer that writes full score rows itself (densescore.hip) takes from score.hip (host functions): room for n rows of
-// h->scores and n lists of h->ranked (grown after the stream has drained), and scorer_enqueue's filter + ranking of those rows --
-// score_rank_kernel where score_row_fits_lds, the WideRanker otherwise; keep_scores leaves the filtered rows in h->scores.
-void grow_score_rows(ScorerHandle *h, int n, int cutoff);
-void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                       bool keep_scores);
-// ease.hip: the weights W = P / (-diag P) of an inverted matrix where they stand in HBM (n x n floats, row pitch *ld), scaled now if
-// they were not yet; returns with the handle's stream drained.  MI355REC_E_INVALID without a successful invert.
-void ease_weights_device(mi355rec_ease *h, const float **W, int64_t *ld, int *n);
 // ---- candidate rows: each user ranks a short list of items of its own (Evaluator.py:455-539, EvaluatorNegativeItemSample) ----------
 constexpr int CAND_MAX = 4096;          // longest candidate row: one block_rank_emit (topk.cuh) over the whole row
 
@@ -95,24 +36,110 @@ struct CandidateRows {
     int longest;            // entries of the longest row (sizes the LDS candidate buffer)
 };
 
+// What every scorer is: recommend / recommend_candidates and the evaluator's add_from_scorer see these members only.  The members
+// are defined next to the scorer's kernels (score.hip, cand.hip, densescore.hip, itemscore.hip).
+struct ScorerHandle : Handle {
+    WideRanker wide;
+    int n_users = 0, n_items = 0;       // rows that can be asked for, width of a score row
+    DeviceBuffer<int> seen_ptr, seen_idx, users, ranked;
+    DeviceBuffer<int> cand_ptr, cand_idx;   // the candidate rows of the last mi355rec_*scorer_recommend_candidates
+    DeviceBuffer<float> scores;
+    DeviceBuffer<unsigned char> allowed;
+
+    // Score + rank, enqueued on the handle's stream.  users: n device user ids; allowed: nullable device mask of n_items bytes;
+    // keep_scores: leave the filtered score rows in `scores` (the public functions' return_scores).
+    virtual Ranking enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) = 0;
+    // The same over candidate rows: only a user's candidates are ranked (value descending, ties towards the lower item id), after
+    // the same seen / mask filters, and no n x n_items score matrix is kept unless the rows have to be accumulated in HBM.  `timer`
+    // spans the candidate kernel(s) (recommend_candidates reports it as kernel_ms and call_ms); `call_timer` is not used.
+    virtual Ranking enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                       const CandidateRows &rows) = 0;
+    // the scorer's own complaint about a user id outside [0, n_users): "user id %d out of range" unless overridden
+    [[noreturn]] virtual void bad_user(int user) const;
+    [[noreturn]] void cold_user(int user) const;    // the reference's "Cold users not allowed..." (factor and item-vector models)
+    // the stats of a finished recommend() that depend on the scorer: its timers, its flops and bytes
+    virtual void fill_recommend_stats(const int32_t *user_ids, int n) = 0;
+
+    // Room for that many cells of `ranked` and `scores`.  Buffers only grow after the stream has drained: a caller that does not
+    // synchronise between blocks -- the holdout evaluator -- may still have kernels reading the old ones.  `wide_cells` is what the
+    // WideRanker is about to be asked for (0: nothing): it grows its own buffers, and is drained for here as well.
+    void reserve(size_t ranked_cells, size_t score_cells, size_t wide_cells);
+
+protected:
+    ~ScorerHandle() = default;          // (handle_destroy deletes through the exact type)
+};
+
+}  // namespace mi355rec
+
+struct mi355rec_scorer final : mi355rec::ScorerHandle {      // `timer`: the GEMM dispatch; `call_timer`: GEMM + ranking
+    int k = 0, use_bias = 0;
+    float mu = 0.f;
+    mi355rec::DeviceBuffer<float> U, V, bu, bi;
+
+    mi355rec::Ranking enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) override;
+    // U[u] . V[c] for the candidates alone (cand.hip): no GEMM, no score matrix
+    mi355rec::Ranking enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                         const mi355rec::CandidateRows &rows) override;
+    [[noreturn]] void bad_user(int user) const override { cold_user(user); }
+    void fill_recommend_stats(const int32_t *user_ids, int n) override;
+    ~mi355rec_scorer() { shutdown(); }
+};
+
+struct mi355rec_spscorer final : mi355rec::ScorerHandle {    // `timer`: the scoring dispatch
+    int n_mid = 0;
+    mi355rec::DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx;
+    mi355rec::DeviceBuffer<float> a_val, b_val;
+    double nnz_a = 0, nnz_b = 0;
+
+    mi355rec::Ranking enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) override;
+    // the row is accumulated as before and the candidates are gathered from it (cand.hip)
+    mi355rec::Ranking enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                         const mi355rec::CandidateRows &rows) override;
+    void fill_recommend_stats(const int32_t *user_ids, int n) override;
+    ~mi355rec_spscorer() { shutdown(); }
+};
+
+struct mi355rec_dscorer final : mi355rec::ScorerHandle {     // densescore.hip.  `timer`: the scoring dispatch; `call_timer`: scoring + ranking
+    int n_mid = 0, unroll = 0;
+    int64_t ldb = 0;                                 // floats between two rows of B (n_items rounded up to 4)
+    mi355rec::DeviceBuffer<int> a_ptr, a_idx;        // A as stored: the order of a row's cells is the order of the sum
+    mi355rec::DeviceBuffer<float> a_val, B;
+    std::vector<int> a_ptr_host;                     // (the stats count the stored cells of a batch's profiles)
+
+    mi355rec::Ranking enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) override;
+    mi355rec::Ranking enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                                         const mi355rec::CandidateRows &rows) override;
+    void fill_recommend_stats(const int32_t *user_ids, int n) override;
+    ~mi355rec_dscorer() { shutdown(); }
+};
+
+namespace mi355rec {
+
+// The bodies of mi355rec_*scorer_recommend (score.hip) and mi355rec_*scorer_recommend_candidates (cand.hip; row r of the candidate
+// CSR belongs to user_ids[r]): the arguments are checked, user ids, candidate rows and the item mask go up, the scorer enqueues,
+// the lists (and the score rows, when asked for) come down, the stats of the call are filled in.
+void recommend(ScorerHandle *h, const int32_t *user_ids, int n, int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked,
+               float *scores);
+void recommend_candidates(ScorerHandle *h, const int32_t *user_ids, int n, const int32_t *cand_indptr, const int32_t *cand_indices,
+                          int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked);
+
+// What a scorer that writes full score rows itself (densescore.hip) takes from score.hip (a host function): the factor scorer's
+// filter + ranking of h->scores[n][n_items] -- score_rank_kernel where score_row_fits_lds, the WideRanker otherwise; keep_scores
+// leaves the filtered rows in h->scores.  The caller has reserved the rows and the lists.
+void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                       bool keep_scores);
+// ease.hip: the weights W = P / (-diag P) of an inverted matrix where they stand in HBM (n x n floats, row pitch *ld), scaled now if
+// they were not yet; returns with the handle's stream drained.  MI355REC_E_INVALID without a successful invert.
+void ease_weights_device(mi355rec_ease *h, const float **W, int64_t *ld, int *n);
+
 // Host check of a candidate CSR: monotone indptr starting at 0, ids inside [0, n_items) and strictly ascending in every row
 // (MI355REC_E_INVALID), no row longer than CAND_MAX (MI355REC_E_UNSUPPORTED).  Returns the length of the longest row.
 int check_candidate_rows(const int32_t *indptr, const int32_t *indices, int n_rows, int n_items);
 void check_candidate_cutoff(int cutoff);    // a list wider than MAX_TOPK (topk.cuh) is MI355REC_E_UNSUPPORTED: the one place that says so
 
-// scorer_enqueue / spscorer_enqueue over candidate rows: only a user's candidates are ranked (value descending, ties towards the
-// lower item id), after the same seen / mask filters.  The factor scorer computes U[u] . V[c] for the candidates alone -- no GEMM, no
-// score matrix; the sparse scorer accumulates its row as before and gathers the candidates from it.  `timer` spans the candidate
-// kernel(s) (mi355rec_*scorer_recommend_candidates reports it as kernel_ms and call_ms); `call_timer` is not used.
-Ranking scorer_enqueue_candidates(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                                  const CandidateRows &rows);
-Ranking spscorer_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
-                                    const unsigned char *allowed, const CandidateRows &rows);
-Ranking dscorer_enqueue_candidates(mi355rec_dscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                                   const CandidateRows &rows);
 // what cand.hip takes from score.hip (host functions): whether a score row of n_items floats is ranked in LDS at this cutoff, and
-// spscorer_enqueue's accumulation of rows that are not -- h->scores[b][n_items] = A[users[b], :] . B, zeroed first, unfiltered, not
-// ranked; the caller has grown h->scores.
+// mi355rec_spscorer::enqueue's accumulation of rows that are not -- h->scores[b][n_items] = A[users[b], :] . B, zeroed first,
+// unfiltered, not ranked; the caller has reserved h->scores.
 bool score_row_fits_lds(int n_items, int cutoff);
 void spscorer_enqueue_wide_rows(mi355rec_spscorer_t h, const int *users, int n);
 // C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's

@@ -305,37 +305,51 @@ bool fits_lds_rank(int n_items, int cutoff) {
 }
 
 }  // namespace
+
+void ScorerHandle::bad_user(int user) const { fail(MI355REC_E_INVALID, "user id %d out of range", user); }
+
+void ScorerHandle::cold_user(int user) const {
+    fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d", n_users, user);
+}
+
+void ScorerHandle::reserve(size_t ranked_cells, size_t score_cells, size_t wide_cells) {
+    if (ranked.count < ranked_cells || scores.count < score_cells || wide.capacity < wide_cells) {
+        MI_HIP(hipStreamSynchronize(stream));
+        if (ranked.count < ranked_cells) ranked.alloc(ranked_cells);
+        if (scores.count < score_cells) scores.alloc(score_cells);
+    }
+}
+
+void recommend(ScorerHandle *h, const int32_t *user_ids, int n, int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked,
+               float *scores) {
+    MI_REQUIRE(h && user_ids && ranked, "NULL argument");
+    MI_REQUIRE(n > 0, "empty user batch");
+    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
+    for (int i = 0; i < n; ++i)
+        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) h->bad_user(user_ids[i]);
+    ensure_device();
+    hipStream_t s = h->stream;
+    if (h->users.count < (size_t)n) {
+        MI_HIP(hipStreamSynchronize(s));
+        h->users.alloc(n);
+    }
+    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
+    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
+    h->enqueue(h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
+    h->ranked.download(ranked, (size_t)n * cutoff, s);
+    if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
+    MI_HIP(hipStreamSynchronize(s));
+    h->stats = mi355rec_stats{};
+    h->fill_recommend_stats(user_ids, n);
+    h->stats.n_launches = h->stats.n_timed = 1;
+    h->stats.n_units = n;
+}
+
 }  // namespace mi355rec
 
 using namespace mi355rec;
 
 namespace {
-// The body of mi355rec_scorer_recommend and mi355rec_spscorer_recommend: user ids and the item mask go up, `enqueue` scores and
-// ranks, the lists (and the score rows, when asked for) come down, `fill_stats` reads the handle's timers.  `bad_user` raises the
-// scorer's own complaint about a user id.
-template <class H, class Enqueue, class BadUser, class FillStats>
-void recommend(H *h, const int32_t *user_ids, int n, int cutoff, int remove_seen, const uint8_t *item_allowed, int32_t *ranked,
-               float *scores, Enqueue enqueue, BadUser bad_user, FillStats fill_stats) {
-    MI_REQUIRE(h && user_ids && ranked, "NULL argument");
-    MI_REQUIRE(n > 0, "empty user batch");
-    MI_REQUIRE(cutoff >= 1 && cutoff <= h->n_items, "cutoff must be in [1, n_items]");
-    for (int i = 0; i < n; ++i)
-        if (user_ids[i] < 0 || user_ids[i] >= h->n_users) bad_user(user_ids[i]);
-    ensure_device();
-    hipStream_t s = h->stream;
-    if (h->users.count < (size_t)n) h->users.alloc(n);
-    MI_HIP(hipMemcpyAsync(h->users.ptr, user_ids, sizeof(int) * n, hipMemcpyHostToDevice, s));
-    if (item_allowed) MI_HIP(hipMemcpyAsync(h->allowed.ptr, item_allowed, h->n_items, hipMemcpyHostToDevice, s));
-    enqueue(h, h->users.ptr, n, cutoff, remove_seen, item_allowed ? h->allowed.ptr : nullptr, scores != nullptr);
-    h->ranked.download(ranked, (size_t)n * cutoff, s);
-    if (scores) h->scores.download(scores, (size_t)n * h->n_items, s);
-    MI_HIP(hipStreamSynchronize(s));
-    h->stats = mi355rec_stats{};
-    fill_stats();
-    h->stats.n_launches = h->stats.n_timed = 1;
-    h->stats.n_units = n;
-}
-
 void upload_model(mi355rec_scorer *h, const float *U, const float *V, const float *bu, const float *bi, float mu) {
     hipStream_t s = h->stream;
     MI_HIP(hipMemcpyAsync(h->U.ptr, U, sizeof(float) * (size_t)h->n_users * h->k, hipMemcpyHostToDevice, s));
@@ -390,18 +404,6 @@ void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const floa
     MI_HIP(hipGetLastError());
 }
 
-// Room for n score rows and their lists.  Buffers only grow after the stream has drained (a caller that does not synchronise between
-// blocks -- the holdout evaluator -- may still have kernels reading the old ones).
-void grow_score_rows(ScorerHandle *h, int n, int cutoff) {
-    const bool wide = !fits_lds_rank(h->n_items, cutoff);
-    if (h->ranked.count < (size_t)n * cutoff || h->scores.count < (size_t)n * h->n_items ||
-        (wide && h->wide.capacity < (size_t)n * h->n_items)) {
-        MI_HIP(hipStreamSynchronize(h->stream));
-        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
-        if (h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
-    }
-}
-
 // The filter + rank half of a full-row scorer: h->scores[n][n_items], unfiltered, -> h->ranked[n][cutoff].
 void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                        bool keep_scores) {
@@ -424,41 +426,35 @@ void rank_rows_enqueue(ScorerHandle *h, const int *users, int n, int cutoff, int
     MI_HIP(hipGetLastError());
 }
 
+}  // namespace mi355rec
+
 // The score + rank half of mi355rec_scorer_recommend: enqueued on the scorer's stream, user ids and the item mask already in
-// device memory; the ranked lists stay in h->ranked.
-Ranking scorer_enqueue(mi355rec_scorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                       bool keep_scores) {
-    hipStream_t s = h->stream;
-    grow_score_rows(h, n, cutoff);
-    h->call_timer.start(s);
+// device memory; the ranked lists stay in `ranked`.
+Ranking mi355rec_scorer::enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) {
+    hipStream_t s = stream;
+    const size_t cells = (size_t)n * n_items;
+    reserve((size_t)n * cutoff, cells, fits_lds_rank(n_items, cutoff) ? 0 : cells);
+    call_timer.start(s);
     ScoreParams sp{};
-    sp.n_users = h->n_users; sp.n_items = h->n_items; sp.k = h->k; sp.use_bias = h->use_bias;
-    sp.U = h->U.ptr; sp.V = h->V.ptr; sp.bu = h->bu.ptr; sp.bi = h->bi.ptr; sp.mu = h->mu;
-    sp.users = users; sp.n_batch = n; sp.scores = h->scores.ptr;
-    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(h->n_items, TN), div_up(n, TM)), dim3(256), 0, s, h->timer.t0,
-                          h->timer.t1, 0, sp);
-    rank_rows_enqueue(h, users, n, cutoff, remove_seen, allowed, keep_scores);
-    h->call_timer.stop(s);
-    return Ranking{h->ranked.ptr, s};
+    sp.n_users = n_users; sp.n_items = n_items; sp.k = k; sp.use_bias = use_bias;
+    sp.U = U.ptr; sp.V = V.ptr; sp.bu = bu.ptr; sp.bi = bi.ptr; sp.mu = mu;
+    sp.users = users; sp.n_batch = n; sp.scores = scores.ptr;
+    hipExtLaunchKernelGGL(score_gemm_kernel, dim3(div_up(n_items, TN), div_up(n, TM)), dim3(256), 0, s, timer.t0, timer.t1, 0, sp);
+    rank_rows_enqueue(this, users, n, cutoff, remove_seen, allowed, keep_scores);
+    call_timer.stop(s);
+    return Ranking{ranked.ptr, s};
 }
 
-}  // namespace mi355rec
+void mi355rec_scorer::fill_recommend_stats(const int32_t *, int n) {
+    stats.call_ms = call_timer.elapsed_ms();
+    stats.kernel_ms = timer.elapsed_ms();
+    stats.algorithmic_flops = 2.0 * (double)n * n_items * k;
+    stats.algorithmic_bytes = 4.0 * ((double)n * k + (double)n_items * k + (double)n * n_items);
+}
 
 extern "C" int mi355rec_scorer_recommend(mi355rec_scorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                          int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
-    return guarded([&] {
-        recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores, scorer_enqueue,
-                  [&](int u) {
-                      fail(MI355REC_E_INVALID, "Cold users not allowed. Users in trained model are %d, requested prediction for user %d",
-                           h->n_users, u);
-                  },
-                  [&] {
-                      h->stats.call_ms = h->call_timer.elapsed_ms();
-                      h->stats.kernel_ms = h->timer.elapsed_ms();
-                      h->stats.algorithmic_flops = 2.0 * (double)n * h->n_items * h->k;
-                      h->stats.algorithmic_bytes = 4.0 * ((double)n * h->k + (double)h->n_items * h->k + (double)n * h->n_items);
-                  });
-    });
+    return guarded([&] { recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores); });
 }
 
 extern "C" int mi355rec_scorer_get_stats(mi355rec_scorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
@@ -574,51 +570,40 @@ extern "C" int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_user
     });
 }
 
-namespace mi355rec {
-// The score + rank half of mi355rec_spscorer_recommend (see scorer_enqueue).
-Ranking spscorer_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
-                         bool keep_scores) {
-    hipStream_t s = h->stream;
-    const bool in_lds = fits_lds_rank(h->n_items, cutoff);
-    const bool need_scores = keep_scores || !in_lds;
-    if (h->ranked.count < (size_t)n * cutoff || (need_scores && h->scores.count < (size_t)n * h->n_items) ||
-        (!in_lds && h->wide.capacity < (size_t)n * h->n_items)) {
-        MI_HIP(hipStreamSynchronize(s));
-        if (h->ranked.count < (size_t)n * cutoff) h->ranked.alloc((size_t)n * cutoff);
-        if (need_scores && h->scores.count < (size_t)n * h->n_items) h->scores.alloc((size_t)n * h->n_items);
-    }
+// The score + rank half of mi355rec_spscorer_recommend (see mi355rec_scorer::enqueue).  The score rows are kept only where somebody
+// reads them: the caller, or the wide ranking.
+Ranking mi355rec_spscorer::enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) {
+    hipStream_t s = stream;
+    const bool in_lds = fits_lds_rank(n_items, cutoff);
+    const size_t cells = (size_t)n * n_items;
+    reserve((size_t)n * cutoff, keep_scores || !in_lds ? cells : 0, in_lds ? 0 : cells);
     SpScoreParams p{};
-    p.n_out = h->n_items; p.n_pad = (h->n_items + 3) & ~3; p.cutoff = cutoff;
+    p.n_out = n_items; p.n_pad = (n_items + 3) & ~3; p.cutoff = cutoff;
     p.remove_seen = remove_seen; p.write_back = keep_scores;
-    p.a_ptr = h->a_ptr.ptr; p.a_idx = h->a_idx.ptr; p.a_val = h->a_val.ptr;
-    p.b_ptr = h->b_ptr.ptr; p.b_idx = h->b_idx.ptr; p.b_val = h->b_val.ptr;
-    p.users = users; p.seen_ptr = h->seen_ptr.ptr; p.seen_idx = h->seen_idx.ptr;
+    p.a_ptr = a_ptr.ptr; p.a_idx = a_idx.ptr; p.a_val = a_val.ptr;
+    p.b_ptr = b_ptr.ptr; p.b_idx = b_idx.ptr; p.b_val = b_val.ptr;
+    p.users = users; p.seen_ptr = seen_ptr.ptr; p.seen_idx = seen_idx.ptr;
     p.allowed = allowed;
-    p.scores = h->scores.ptr; p.ranked = h->ranked.ptr;
+    p.scores = scores.ptr; p.ranked = ranked.ptr;
     if (in_lds) {
         const size_t lds = (size_t)p.n_pad * 4 + (size_t)AUX_WORDS * 4;
         auto k = spscore_kernel<1024>;
         MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipExtLaunchKernelGGL(k, dim3(n), dim3(1024), (unsigned)lds, s, h->timer.t0, h->timer.t1, 0, p);
+        hipExtLaunchKernelGGL(k, dim3(n), dim3(1024), (unsigned)lds, s, timer.t0, timer.t1, 0, p);
     } else {
-        MI_HIP(hipMemsetAsync(h->scores.ptr, 0, sizeof(float) * (size_t)n * h->n_items, s));
-        hipExtLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, h->timer.t0, h->timer.t1, 0, p);
-        h->wide.rank(s, h->scores.ptr, n, h->n_items, cutoff, users, h->seen_ptr.ptr, h->seen_idx.ptr, p.allowed, remove_seen,
-                     h->ranked.ptr);
+        MI_HIP(hipMemsetAsync(scores.ptr, 0, sizeof(float) * cells, s));
+        hipExtLaunchKernelGGL(spscore_wide_kernel, dim3(n), dim3(1024), 0, s, timer.t0, timer.t1, 0, p);
+        wide.rank(s, scores.ptr, n, n_items, cutoff, users, seen_ptr.ptr, seen_idx.ptr, p.allowed, remove_seen, ranked.ptr);
     }
     MI_HIP(hipGetLastError());
-    return Ranking{h->ranked.ptr, s};
+    return Ranking{ranked.ptr, s};
 }
 
-}  // namespace mi355rec
+void mi355rec_spscorer::fill_recommend_stats(const int32_t *, int) { stats.kernel_ms = stats.call_ms = timer.elapsed_ms(); }
 
 extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                            int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
-    return guarded([&] {
-        recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores, spscorer_enqueue,
-                  [](int u) { fail(MI355REC_E_INVALID, "user id %d out of range", u); },
-                  [&] { h->stats.kernel_ms = h->stats.call_ms = h->timer.elapsed_ms(); });
-    });
+    return guarded([&] { recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores); });
 }
 
 extern "C" int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
@@ -630,8 +615,8 @@ namespace mi355rec {
 
 bool score_row_fits_lds(int n_items, int cutoff) { return fits_lds_rank(n_items, cutoff); }
 
-// spscorer_enqueue's accumulation for rows in HBM, without the ranking: h->scores[b][n_items] = A[users[b], :] . B, unfiltered.
-// The caller has grown h->scores (after the stream had drained).
+// mi355rec_spscorer::enqueue's accumulation for rows in HBM, without the ranking: h->scores[b][n_items] = A[users[b], :] . B,
+// unfiltered.  The caller has reserved h->scores.
 void spscorer_enqueue_wide_rows(mi355rec_spscorer_t h, const int *users, int n) {
     hipStream_t s = h->stream;
     SpScoreParams p{};

@@ -219,9 +219,8 @@ class _EASELogic:
             if ease is not None:
                 ease.close()
             builder.close()
-        if getattr(self, "_dense_scorer", None) is not None and not self.dense_device_scorable():
-            self._dense_scorer.close()              # (a sparse W after a dense one: n_items^2 floats of HBM go back)
-            self._dense_scorer = self._dense_scorer_src = None
+        if isinstance(self, GpuSimilarityScoringMixin) and not self.dense_device_scorable():
+            self.release_dense_scorer()             # (a sparse W after a dense one: n_items^2 floats of HBM go back)
         info.update(fill_s=t_filled - t_start, invert_s=t_inverted - t_filled, finish_s=time.perf_counter() - t_inverted,
                     scoring=self._scoring_now())
         self.fit_info = info

@@ -21,7 +21,7 @@ import numpy as np
 import scipy.sparse as sps
 
 from . import _native as N
-from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin, allowed_items
+from .scoring import _ScoringMixin, allowed_items
 
 # EvaluatorMetrics order (Evaluator.py:20-40), without DIVERSITY_SIMILARITY
 METRICS = ["ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", "MRR", "NDCG", "F1", "HIT_RATE", "ARHR", "NOVELTY",
@@ -215,24 +215,33 @@ class EvaluatorHoldout_MI355X(N.Handle):
 
     def _run(self, rec, block_size):
         """Every block of users through the fused path of the recommender's device scorer, or through its recommend()."""
-        block = int(block_size) if block_size else self._block_size()
-        if isinstance(rec, GpuScoringMixin):
-            self._run_fused(rec._get_scorer(), "add_scorer", rec, block)
-        elif isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
-            self._run_fused(rec._get_sparse_scorer(), "add_spscorer", rec, block)
-        elif isinstance(rec, GpuSimilarityScoringMixin) and rec.dense_device_scorable():
-            self._run_fused(rec._get_dense_scorer(), "add_dscorer", rec, block)
-        elif isinstance(rec, GpuItemScoreMixin):       # (no n x n_items score buffer bounds a launch: fewer, larger blocks)
-            self._run_fused(rec._get_item_scorer(), "add_itemscorer", rec,
-                            int(block_size) if block_size else min(self.FUSED_BLOCK, len(self.users_to_evaluate)))
-        else:
+        self._dispatch(rec, block_size, "rows")
+
+    def _dispatch(self, rec, block_size, path):
+        """path: what a device scorer ranks -- "rows" (entry point EVAL_ADD), "candidates" (EVAL_ADD_candidates) -- or None: every
+        recommender through recommend()."""
+        scorer = rec.device_scorer() if path and isinstance(rec, _ScoringMixin) else None
+        large = scorer is not None and path in scorer.EVAL_LARGE_BLOCKS     # (no n x n_items score buffer bounds a launch)
+        block = int(block_size) if block_size else (min(self.FUSED_BLOCK, len(self.users_to_evaluate)) if large else self._block_size())
+        if scorer is None:
             self._run_lists(rec, block)
+        else:
+            self._run_fused(scorer, scorer.EVAL_ADD + ("" if path == "rows" else "_" + path), rec, block)
 
     def _run_fused(self, scorer, add, rec, block):
         allowed = allowed_items(rec, remove_custom_items_flag=self.ignore_items_flag)
         for start in range(0, len(self.users_to_evaluate), block):
             n = min(block, len(self.users_to_evaluate) - start)
             self._call(add, scorer._h, start, n, int(bool(self.exclude_seen)), N.ptr(allowed))
+
+    def _put_list(self, table, r, items):
+        """A user's list, checked, into row r of a block's -1 padded table."""
+        items = np.asarray(items).ravel()
+        if len(items) > self.width:
+            raise ValueError("{}: a list of {} items for cutoff {}".format(self.EVALUATOR_NAME, len(items), self.max_cutoff))
+        if len(items) and (items.min() < 0 or items.max() >= self.n_items):
+            raise ValueError("{}: recommended item id outside [0, {})".format(self.EVALUATOR_NAME, self.n_items))
+        table[r, :len(items)] = items
 
     def _run_lists(self, rec, block):
         users = self.users_to_evaluate
@@ -244,12 +253,7 @@ class EvaluatorHoldout_MI355X(N.Handle):
                 raise ValueError("{}: recommend() returned {} lists for {} users".format(self.EVALUATOR_NAME, len(lists), len(batch)))
             table = np.full((len(batch), self.width), -1, np.int32)
             for r, items in enumerate(lists):
-                items = np.asarray(items).ravel()
-                if len(items) > self.width:
-                    raise ValueError("{}: a list of {} items for cutoff {}".format(self.EVALUATOR_NAME, len(items), self.max_cutoff))
-                if len(items) and (items.min() < 0 or items.max() >= self.n_items):
-                    raise ValueError("{}: recommended item id outside [0, {})".format(self.EVALUATOR_NAME, self.n_items))
-                table[r, :len(items)] = items
+                self._put_list(table, r, items)
             self._call("add_lists", start, len(batch), N.ptr(table))
 
     def per_user_values(self):
@@ -318,17 +322,7 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
         return rows.indices[rows.indptr[user]:rows.indptr[user + 1]]
 
     def _run(self, rec, block_size):
-        n_eval = len(self.users_to_evaluate)
-        if self.candidates_on_device and isinstance(rec, GpuScoringMixin):
-            self._run_fused(rec._get_scorer(), "add_scorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
-        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.device_scorable():
-            self._run_fused(rec._get_sparse_scorer(), "add_spscorer_candidates", rec, int(block_size) if block_size else self._block_size())
-        elif self.candidates_on_device and isinstance(rec, GpuSimilarityScoringMixin) and rec.dense_device_scorable():
-            self._run_fused(rec._get_dense_scorer(), "add_dscorer_candidates", rec, int(block_size) if block_size else self._block_size())
-        elif self.candidates_on_device and isinstance(rec, GpuItemScoreMixin):
-            self._run_fused(rec._get_item_scorer(), "add_itemscorer_candidates", rec, int(block_size) if block_size else min(self.FUSED_BLOCK, n_eval))
-        else:
-            self._run_lists(rec, int(block_size) if block_size else self._block_size())
+        self._dispatch(rec, block_size, "candidates" if self.candidates_on_device else None)
 
     def _run_lists(self, rec, block):
         """Evaluator.py:519-530: recommend() per user with the user's candidates as items_to_compute; the lists of a block of users go
@@ -343,10 +337,5 @@ class EvaluatorNegativeItemSample_MI355X(EvaluatorHoldout_MI355X):
                                       remove_custom_items_flag=self.ignore_items_flag, return_scores=False)
                 if len(lists) != 1:
                     raise ValueError("{}: recommend() returned {} lists for one user".format(self.EVALUATOR_NAME, len(lists)))
-                items = np.asarray(lists[0]).ravel()
-                if len(items) > self.width:
-                    raise ValueError("{}: a list of {} items for cutoff {}".format(self.EVALUATOR_NAME, len(items), self.max_cutoff))
-                if len(items) and (items.min() < 0 or items.max() >= self.n_items):
-                    raise ValueError("{}: recommended item id outside [0, {})".format(self.EVALUATOR_NAME, self.n_items))
-                table[r, :len(items)] = items
+                self._put_list(table, r, lists[0])
             self._call("add_lists", start, len(batch), N.ptr(table))

@@ -16,7 +16,11 @@ from . import _native as N
 
 
 class _Scorer(N.Handle):
-    """What the two scorers share: recommend() over mi355rec_<kind>_recommend; n_items is the width of a score row."""
+    """What the scorers share: recommend() over mi355rec_<kind>_recommend; n_items is the width of a score row.  Two class
+    attributes tell the device evaluators (evaluation.py) how to drive a scorer."""
+    EVAL_ADD = None             # its entry point of the evaluator: mi355rec_eval_<EVAL_ADD>, and <EVAL_ADD>_candidates
+    EVAL_LARGE_BLOCKS = ()      # of "rows" / "candidates": the paths that keep no (users x n_items) score buffer, so that a launch
+                                # takes the evaluator's FUSED_BLOCK users instead of the reference's block
 
     def recommend(self, user_id_array, cutoff, remove_seen=True, allowed_items=None, return_scores=False):
         """ranked: int32 (n, cutoff) with -1 padding; scores: float32 (n, n_items) with -inf for filtered items."""
@@ -50,6 +54,8 @@ class _Scorer(N.Handle):
 
 class MI355XScorer(_Scorer):
     _PREFIX = "mi355rec_scorer"
+    EVAL_ADD = "add_scorer"
+    EVAL_LARGE_BLOCKS = ("candidates",)
 
     def __init__(self, USER_factors, ITEM_factors, URM_seen, USER_bias=None, ITEM_bias=None, GLOBAL_bias=0.0):
         U, V = N.as_f32(USER_factors), N.as_f32(ITEM_factors)
@@ -112,22 +118,61 @@ def ranked_lists(ranked):
 
 
 class _ScoringMixin:
-    """What the two mixins below share: recommend() of BaseRecommender (same signature, same return values) over the ranked array of
-    a device scorer, and dropping that scorer.  A subclass names the attributes that cache its scorer and what it was built from
-    (`_SCORER_ATTRS`) and builds or re-uses the scorer in `_scorer_for(users)`."""
-    _SCORER_ATTRS = None
+    """What the mixins below share: recommend() of BaseRecommender (same signature, same return values) over the ranked array of a
+    device scorer, the cache of that scorer, and dropping it.  A subclass names its cache slots (`_SCORER_ATTRS`: pairs of the
+    attribute that holds a scorer and the one that holds what it was built from), says which scorer serves the model now
+    (`device_scorer()`) and describes each scorer to `_cached_scorer`.
+
+    The cache rule: a slot holds STRONG references to the objects its scorer was built from and compares by identity (an id() of a
+    freed object can be reused by its successor) plus a content `_fingerprint` (in-place edits).  A new scorer is built when
+    URM_train is replaced or the layout changes; other values in the same layout are an `update` -- a new scorer where the scorer
+    has none.  So the scorer follows early-stopping's _prepare_model_for_validation / best-model swaps and set_URM_train by itself."""
+    _SCORER_ATTRS = ()
+    _ASSERT_WARM_USERS = False      # the reference's cold-user assertion of the factor and non-personalized models
 
     def invalidate_scorer(self):
         """Forget the device copy of the model: the next recommend() uploads it again.  The caches notice REPLACED arrays (identity)
         and wholesale in-place changes (a strided 256-element fingerprint -- an optimiser step moves practically every cell); code
         that edits a few rows of a factor matrix in place (folding in cold users, say) must call this.  The package's own training
         loops call it from _prepare_model_for_validation."""
-        scorer_attr, src_attr = self._SCORER_ATTRS
-        setattr(self, src_attr, None)
+        for slot in self._SCORER_ATTRS:
+            self._drop_scorer(slot)
+
+    def _drop_scorer(self, slot):
+        scorer_attr, src_attr = slot
         scorer = getattr(self, scorer_attr)
+        setattr(self, scorer_attr, None)
+        setattr(self, src_attr, None)
         if scorer is not None:
             scorer.close()
-            setattr(self, scorer_attr, None)
+
+    def _cached_scorer(self, slot, sources, prints, build, update=None, new_layout=lambda scorer: False):
+        """The scorer of `slot` for the current model.  sources: {name: object the scorer is made from}; prints: their fingerprints;
+        build(): a new scorer; update(scorer): other values into the one there is (None: build again); new_layout(scorer): it
+        cannot take them."""
+        scorer_attr, src_attr = slot
+        scorer, old = getattr(self, scorer_attr), getattr(self, src_attr)
+        changed = old is None or old["print"] != prints or any(old.get(name) is not obj for name, obj in sources.items())
+        if scorer is None or old is None or old["urm"] is not self.URM_train or new_layout(scorer) or (changed and update is None):
+            self._drop_scorer(slot)
+            scorer = build()
+            setattr(self, scorer_attr, scorer)
+        elif changed:
+            update(scorer)
+        setattr(self, src_attr, dict(sources, print=prints, urm=self.URM_train))
+        return scorer
+
+    def device_scorer(self):
+        """The scorer that serves the model now -- under recommend() and under the device evaluators' fused path -- or None when the
+        model has to go through the base class's recommend()."""
+        raise NotImplementedError("{}: device_scorer".format(type(self).__name__))
+
+    def _scorer_for(self, users):
+        scorer = self.device_scorer()
+        assert not self._ASSERT_WARM_USERS or scorer.n_users > np.max(users), \
+            "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
+                self.RECOMMENDER_NAME, scorer.n_users, np.max(users))
+        return scorer
 
     def recommend(self, user_id_array, cutoff=None, remove_seen_flag=True, items_to_compute=None, remove_top_pop_flag=False,
                   remove_custom_items_flag=False, return_scores=False):
@@ -144,49 +189,34 @@ class _ScoringMixin:
 
 
 class GpuScoringMixin(_ScoringMixin):
-    """recommend() of BaseRecommender (same signature, same return values) served by MI355XScorer.  The scorer is
-    (re)built lazily from the host attributes USER_factors / ITEM_factors[/biases] and URM_train, so it follows
-    early-stopping's _prepare_model_for_validation / best-model swaps and set_URM_train automatically.  The cache holds
-    STRONG references to the objects it was built from and compares by identity (an id() of a freed object can be reused
-    by its successor) plus a content fingerprint (in-place edits)."""
+    """recommend() of BaseRecommender (same signature, same return values) served by MI355XScorer, (re)built lazily from the host
+    attributes USER_factors / ITEM_factors[/biases] and URM_train."""
     _scorer = None
     _scorer_src = None
-    _SCORER_ATTRS = ("_scorer", "_scorer_src")
-
-    def _scorer_sources(self):
-        src = [self.USER_factors, self.ITEM_factors]
-        if self.use_bias:
-            src += [self.USER_bias, self.ITEM_bias, np.asarray(self.GLOBAL_bias)]
-        return src
+    _SCORER_ATTRS = (("_scorer", "_scorer_src"),)
+    _ASSERT_WARM_USERS = True
 
     def _get_scorer(self):
-        src = self._scorer_sources()
-        prints = [_fingerprint(a) for a in src]
-        bias = dict(USER_bias=self.USER_bias, ITEM_bias=self.ITEM_bias, GLOBAL_bias=self.GLOBAL_bias) if self.use_bias else {}
-        old = self._scorer_src
-        rebuild = (self._scorer is None or self._scorer.use_bias != bool(self.use_bias) or old["urm"] is not self.URM_train
-                   or self._scorer.n_factors != np.asarray(self.USER_factors).shape[1])
-        if rebuild:
-            if self._scorer is not None:
-                self._scorer.close()
-            self._scorer = MI355XScorer(self.USER_factors, self.ITEM_factors, self.URM_train, **bias)    # uploads the seen CSR too
-        elif len(old["src"]) != len(src) or any(a is not b for a, b in zip(old["src"], src)) or old["prints"] != prints:
-            self._scorer.update(self.USER_factors, self.ITEM_factors, **bias)
-        self._scorer_src = {"src": src, "prints": prints, "urm": self.URM_train}
-        return self._scorer
+        sources, bias = {"USER_factors": self.USER_factors, "ITEM_factors": self.ITEM_factors}, {}
+        if self.use_bias:
+            bias = dict(USER_bias=self.USER_bias, ITEM_bias=self.ITEM_bias, GLOBAL_bias=self.GLOBAL_bias)
+            sources.update(bias, GLOBAL_bias=np.asarray(self.GLOBAL_bias))
+        return self._cached_scorer(
+            self._SCORER_ATTRS[0], sources, [_fingerprint(a) for a in sources.values()],
+            build=lambda: MI355XScorer(self.USER_factors, self.ITEM_factors, self.URM_train, **bias),    # uploads the seen CSR too
+            update=lambda scorer: scorer.update(self.USER_factors, self.ITEM_factors, **bias),
+            new_layout=lambda scorer: (scorer.use_bias != bool(self.use_bias)
+                                       or scorer.n_factors != np.asarray(self.USER_factors).shape[1]))
 
-    def _scorer_for(self, users):
-        scorer = self._get_scorer()
-        assert scorer.n_users > np.max(users), \
-            "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
-                self.RECOMMENDER_NAME, scorer.n_users, np.max(users))
-        return scorer
+    def device_scorer(self):
+        return self._get_scorer()
 
 
 class MI355XSparseScorer(_Scorer):
     """scores[u] = A[u, :] . B for sparse A, B (ItemKNN / SLIM: A = URM_train, B = W_sparse; UserKNN: A = W_sparse,
     B = URM_train), filtered and ranked on the device like MI355XScorer."""
     _PREFIX = "mi355rec_spscorer"
+    EVAL_ADD = "add_spscorer"
 
     def __init__(self, A, B, URM_seen):
         A, B, seen = A.tocsr(), B.tocsr(), URM_seen.tocsr()
@@ -204,6 +234,7 @@ class MI355XDenseScorer(_Scorer):
     in their storage order (A's indices are used as given, never sorted), product rounded before the add.  `B` is the array, or
     its shape `(n_mid, n_items)` for zero weights that `update` / `set_weights_from` fill later."""
     _PREFIX = "mi355rec_dscorer"
+    EVAL_ADD = "add_dscorer"
 
     def __init__(self, A, B, URM_seen):
         if not sps.isspmatrix_csr(A):
@@ -237,20 +268,19 @@ class MI355XDenseScorer(_Scorer):
 
 class GpuSimilarityScoringMixin(_ScoringMixin):
     """recommend() for BaseItemSimilarityMatrixRecommender / BaseUserSimilarityMatrixRecommender subclasses, served by
-    MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  The scorer is rebuilt whenever W_sparse or
-    URM_train is replaced (fit, early-stopping validation).
+    MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  The sparse scorer has no update: it is rebuilt whenever
+    W_sparse or URM_train is replaced (fit, early-stopping validation) or W_sparse changes in place.
 
     An item-based model whose W_sparse is a dense ndarray is served by MI355XDenseScorer when the class (or the object) sets
     `dense_scoring = "device"`; with the default "host" it is scored by the base class on the host, as before.  The dense scorer has a
-    cache of its own under the same rules: strong references, identity plus `_fingerprint` of W (other weights of the same shape
-    are an update), a new scorer when URM_train is replaced."""
+    cache slot of its own: other weights of the same shape are an update."""
     _SCORER_USER_BASED = False
     _sp_scorer = None
     _sp_scorer_src = None
-    _SCORER_ATTRS = ("_sp_scorer", "_sp_scorer_src")
     dense_scoring = "host"
     _dense_scorer = None
     _dense_scorer_src = None
+    _SCORER_ATTRS = (("_sp_scorer", "_sp_scorer_src"), ("_dense_scorer", "_dense_scorer_src"))
 
     def device_scorable(self):
         """False while W_sparse is a dense array (EASE_R with topK=None keeps the reference's ndarray): the sparse scorer takes a CSR, so
@@ -267,46 +297,32 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
         """The dense scorer for the current W_sparse and URM_train.  `weights_from`: an MI355XEase handle that holds W_sparse's values on
         the device -- they are copied from there instead of being uploaded from the host array."""
         W = self.W_sparse
-        print_now = _fingerprint(W)
-        old = self._dense_scorer_src
-        scorer = self._dense_scorer
-        fresh = scorer is None or old["urm"] is not self.URM_train or (scorer.n_mid, scorer.n_items) != W.shape
-        if fresh:
-            if scorer is not None:
-                scorer.close()
-                self._dense_scorer = None
-            scorer = MI355XDenseScorer(self.URM_train, W.shape if weights_from is not None else W, self.URM_train)
-            self._dense_scorer = scorer
-        if weights_from is not None:
+        on_device = weights_from is not None
+        scorer = self._cached_scorer(
+            self._SCORER_ATTRS[1], {"W": W}, _fingerprint(W),
+            build=lambda: MI355XDenseScorer(self.URM_train, W.shape if on_device else W, self.URM_train),
+            update=lambda scorer: None if on_device else scorer.update(W),
+            new_layout=lambda scorer: (scorer.n_mid, scorer.n_items) != W.shape)
+        if on_device:
             scorer.set_weights_from(weights_from)
-        elif not fresh and (old["W"] is not W or old["print"] != print_now):
-            scorer.update(W)
-        self._dense_scorer_src = {"W": W, "urm": self.URM_train, "print": print_now}
         return scorer
 
-    def invalidate_scorer(self):
-        super().invalidate_scorer()
-        self._dense_scorer_src = None
-        if self._dense_scorer is not None:
-            self._dense_scorer.close()
-            self._dense_scorer = None
-
     def _get_sparse_scorer(self):
-        # strong references + identity (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of
-        # the first, freed matrix can be handed to its successor, so an id() key would score with stale weights)
+        # (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of the first, freed matrix can be
+        # handed to its successor, so an id() key would score with stale weights)
         W = self.W_sparse
-        print_now = (W.shape, W.nnz, _fingerprint(W.data), _fingerprint(W.indices)) if hasattr(W, "nnz") else _fingerprint(W)
-        old = self._sp_scorer_src
-        if self._sp_scorer is None or old["W"] is not W or old["urm"] is not self.URM_train or old["print"] != print_now:
-            if self._sp_scorer is not None:
-                self._sp_scorer.close()
-            A, B = (self.W_sparse, self.URM_train) if self._SCORER_USER_BASED else (self.URM_train, self.W_sparse)
-            self._sp_scorer = MI355XSparseScorer(A, B, self.URM_train)
-            self._sp_scorer_src = {"W": W, "urm": self.URM_train, "print": print_now}
-        return self._sp_scorer
+        A, B = (W, self.URM_train) if self._SCORER_USER_BASED else (self.URM_train, W)
+        prints = (W.shape, W.nnz, _fingerprint(W.data), _fingerprint(W.indices)) if hasattr(W, "nnz") else _fingerprint(W)
+        return self._cached_scorer(self._SCORER_ATTRS[0], {"W": W}, prints, build=lambda: MI355XSparseScorer(A, B, self.URM_train))
 
-    def _scorer_for(self, users):
-        return self._get_dense_scorer() if self.dense_device_scorable() else self._get_sparse_scorer()
+    def device_scorer(self):
+        if self.dense_device_scorable():
+            return self._get_dense_scorer()
+        return self._get_sparse_scorer() if self.device_scorable() else None
+
+    def release_dense_scorer(self):
+        """Give the dense scorer's n_items^2 floats of HBM back (a sparse W_sparse after a dense one)."""
+        self._drop_scorer(self._SCORER_ATTRS[1])
 
 
 class MI355XItemScorer(_Scorer):
@@ -315,6 +331,8 @@ class MI355XItemScorer(_Scorer):
     that order without the user's seen items -- work of cutoff + profile length per user instead of n_items.  A non-finite entry of
     the vector is never listed.  `URM_seen` is a host matrix or a `ResidentURM` (its structure is then copied device to device)."""
     _PREFIX = "mi355rec_itemscorer"
+    EVAL_ADD = "add_itemscorer"
+    EVAL_LARGE_BLOCKS = ("rows", "candidates")
 
     def __init__(self, item_scores, URM_seen):
         vec = N.as_f32(np.asarray(item_scores).ravel())
@@ -345,36 +363,26 @@ class MI355XItemScorer(_Scorer):
 
 class GpuItemScoreMixin(_ScoringMixin):
     """recommend() for recommenders whose scores are one vector shared by all users, served by MI355XItemScorer.  The vector is
-    `_item_score_vector()`; the cache follows the rules of the other two mixins: strong references, identity plus `_fingerprint` of
-    the vector (a new vector of the same length is an update), a new scorer when URM_train is replaced.  `_resident_urm`, when the
-    recommender has one that holds URM_train, also serves as the scorer's seen CSR.  A model restored by load_model is scored
-    without a fit."""
+    `_item_score_vector()`; a new vector of the same length is an update.  `_resident_urm`, when the recommender has one that holds
+    URM_train, also serves as the scorer's seen CSR.  A model restored by load_model is scored without a fit."""
     _item_scorer = None
     _item_scorer_src = None
     _resident_urm = None
-    _SCORER_ATTRS = ("_item_scorer", "_item_scorer_src")
+    _SCORER_ATTRS = (("_item_scorer", "_item_scorer_src"),)
+    _ASSERT_WARM_USERS = True
 
     def _item_score_vector(self):
         raise NotImplementedError("{}: _item_score_vector".format(type(self).__name__))
 
     def _get_item_scorer(self):
         vector = self._item_score_vector()
-        print_now = _fingerprint(vector)
-        old = self._item_scorer_src
-        if self._item_scorer is None or old["urm"] is not self.URM_train:
-            if self._item_scorer is not None:
-                self._item_scorer.close()
-            resident = self._resident_urm
-            seen = resident if resident is not None and resident.matches(self.URM_train) else self.URM_train
-            self._item_scorer = MI355XItemScorer(vector, seen)
-        elif old["vector"] is not vector or old["print"] != print_now:
-            self._item_scorer.update(vector)
-        self._item_scorer_src = {"vector": vector, "print": print_now, "urm": self.URM_train}
-        return self._item_scorer
 
-    def _scorer_for(self, users):
-        scorer = self._get_item_scorer()
-        assert scorer.n_users > np.max(users), \
-            "{}: Cold users not allowed. Users in trained model are {}, requested prediction for users up to {}".format(
-                self.RECOMMENDER_NAME, scorer.n_users, np.max(users))
-        return scorer
+        def build():
+            resident = self._resident_urm
+            return MI355XItemScorer(vector, resident if resident is not None and resident.matches(self.URM_train) else self.URM_train)
+
+        return self._cached_scorer(self._SCORER_ATTRS[0], {"vector": vector}, _fingerprint(vector), build,
+                                   update=lambda scorer: scorer.update(vector))
+
+    def device_scorer(self):
+        return self._get_item_scorer()
