@@ -311,6 +311,9 @@ int mi355rec_mf_set_profiling(mi355rec_mf_t h, int32_t max_timed_launches);
  * LAST mini-batch run, 8 words per task slot {entry, header arrived, first rows arrived, list done, exit, list length,
  * own row written, taken-over item rows written}.  *n receives the number of words available (0 when the handle was created without the variable). */
 int mi355rec_mf_get_phase_ticks(mi355rec_mf_t h, uint64_t *out, int64_t cap, int64_t *n);
+/* The same for the in-LDS schedule's sort kernel, last schedule built: 8 words per mini-batch, stamped by thread 0 of its workgroup
+ * {entry, keys in LDS (drawn or read back), sorted, run heads, once-touched flags, slot scans, headers written, exit}. */
+int mi355rec_mf_get_schedule_ticks(mi355rec_mf_t h, uint64_t *out, int64_t cap, int64_t *n);
 int mi355rec_mf_get_stats(mi355rec_mf_t h, mi355rec_stats *stats);
 void mi355rec_mf_destroy(mi355rec_mf_t h);
 

@@ -14,7 +14,8 @@
 // mini-batch, i.e. two dependent launches and five dependent memory round trips per batch (10.2 us per batch of 1000).
 // This version uses (2) as well and turns the batch into ONE gather kernel with no atomics, no flags and no
 // accumulators:
-//   mf_sample_kernel   one thread per sample of the epoch (counter-based RNG, binary-search rejection);
+//   mf_sample_kernel   one thread per sample of the epoch (counter-based RNG, binary-search rejection) -- or, for an epoch that goes
+//                      through one in-LDS schedule, the same draw inside that schedule's workgroups (schedule_draws);
 //   schedule           the epoch's (row, batch) incidences are grouped (in-LDS radix sort per mini-batch, or one rocPRIM sort of
 //                      the whole stream) into TASKS: one task per row touched
 //                      in a batch, holding the list of that batch's samples which touch the row.  Because every
@@ -75,7 +76,7 @@ struct mi355rec_mf : Handle {
     DeviceBuffer<unsigned> touched;         // fast schedule: (row, mini-batch) bitmap
     DeviceBuffer<int> sorted_slot, qtask, used;
     bool fast_schedule = false;
-    DeviceBuffer<unsigned long long> ticks;
+    DeviceBuffer<unsigned long long> ticks, sched_ticks;
     DeviceBuffer<int4> recs, slot_recs;
     size_t cub_tmp_bytes = 0;
     size_t stream_capacity = 0;      // samples
@@ -294,7 +295,28 @@ FastSchedParams fast_sched_params(mi355rec_mf *h, long long n_samples) {
     // fused sample tasks: BPR only; not in the exact multi-GPU mode, whose exchange slabs hold one row per task slot
     f.fuse = h->cfg.algorithm == MI355REC_MF_BPR && h->shard_rank < 0 && !getenv("MI355REC_MF_NO_FUSE");
     f.fill_all = 1;
+    f.ticks = h->sched_ticks.ptr;
     return f;
+}
+
+// A native epoch whose whole stream goes through ONE in-LDS schedule is drawn by that schedule's workgroups (FastSchedParams::draw):
+// no sampler launch, no epoch-advance launch, no read-back of the stream.  Everything else keeps launch_sampler: replayed streams,
+// streams scheduled FAST_MAX_BATCHES mini-batches at a time, the radix-sort schedule, the group, the exact multi-GPU mode, AsySVD.
+bool schedule_draws(const mi355rec_mf *h);
+
+template <class T>
+void set_draw(FastSchedParams &f, const MfParams<T> &p) {
+    f.draw = 1;
+    f.advance_epoch = 1;
+    f.bpr = f.per == 3;
+    f.sample_negatives = p.sample_negatives;
+    f.n_items = p.n_items;
+    f.quota = p.quota;
+    f.seed = p.seed;
+    f.samples_per_epoch = p.samples_per_epoch;
+    f.first_sample = 0;
+    f.state = p.state;
+    f.indptr = p.indptr; f.indices = p.indices; f.data = p.data;
 }
 
 void enqueue_fast_schedule(mi355rec_mf *h, long long n_samples, long long n_batches, const FastSchedParams *given = nullptr,
@@ -368,17 +390,27 @@ long long schedule_span(const mi355rec_mf *h, long long n_batches) {
     return n_batches;
 }
 
+bool schedule_draws(const mi355rec_mf *h) {
+    const long long nb = batches_per_epoch(h);
+    return h->cfg.algorithm != MI355REC_MF_ASY_SVD && h->shard_rank < 0 && h->fast_schedule && fast_schedule_fits(h, nb) &&
+           schedule_span(h, nb) == nb;
+}
+
 // mini-batches first .. last - 1 of a stream of n_batches, with the schedules and stream ends that fall into that range
 template <class T>
 void enqueue_stream(mi355rec_mf *h, const MfParams<T> &p, long long n_samples, long long n_batches, bool timed, long long first = 0,
-                    long long last = -1) {
+                    long long last = -1, bool draw = false) {
     const bool bpr = h->cfg.algorithm == MI355REC_MF_BPR;
     const long long span = schedule_span(h, n_batches), B = h->cfg.batch_size;
     if (last < 0) last = n_batches;
     for (long long b = first; b < last; ++b) {
         const long long part = b / span * span, local = b - part, part_batches = std::min(span, n_batches - part);
         if (local == 0) {
-            if (span == n_batches) {
+            if (draw) {                 // (schedule_draws: one span on the in-LDS schedule)
+                FastSchedParams f = fast_sched_params(h, n_samples);
+                set_draw(f, p);
+                enqueue_fast_schedule(h, n_samples, n_batches, &f);
+            } else if (span == n_batches) {
                 enqueue_schedule(h, n_samples, n_batches);
             } else {
                 FastSchedParams f = fast_sched_params(h, std::min(n_samples - part * B, part_batches * B));
@@ -414,12 +446,13 @@ void enqueue_asy_steps(mi355rec_mf *h, const MfParams<T> &p, long long n_steps, 
 // part of it that holds mini-batches first .. last - 1: sampler and schedule go with the first part.
 template <class T>
 void enqueue_epoch(mi355rec_mf *h, const MfParams<T> &p, bool timed, long long first = 0, long long last = -1) {
-    if (first == 0) launch_sampler(h, p);
+    const bool draw = schedule_draws(h);
+    if (first == 0 && !draw) launch_sampler(h, p);
     if (h->cfg.algorithm == MI355REC_MF_ASY_SVD) {
         enqueue_asy_steps(h, p, p.samples_per_epoch, timed);
         return;
     }
-    enqueue_stream(h, p, p.samples_per_epoch, batches_per_epoch(h), timed, first, last);
+    enqueue_stream(h, p, p.samples_per_epoch, batches_per_epoch(h), timed, first, last, draw);
 }
 
 // Capture one epoch into graphs of up to GRAPH_SEGMENT mini-batches (once per handle; re-captured only if the stream buffers are
@@ -701,7 +734,10 @@ extern "C" int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *
         h->data.upload(data, h->nnz, s);
         if (h->f64) create_typed<double>(h.get(), U0, V0); else create_typed<float>(h.get(), U0, V0);
         h->par.alloc_zero((size_t)n_users + n_items, s);
-        if (getenv("MI355REC_MF_TICKS")) h->ticks.alloc_zero((size_t)per_sample(h.get()) * cfg->batch_size * 8, s);
+        if (getenv("MI355REC_MF_TICKS")) {
+            h->ticks.alloc_zero((size_t)per_sample(h.get()) * cfg->batch_size * 8, s);
+            h->sched_ticks.alloc_zero((size_t)FAST_MAX_BATCHES * SCHED_STAMPS, s);
+        }
         h->loss_slots.alloc_zero((size_t)per_sample(h.get()) * cfg->batch_size * 4, s);
         h->state.alloc_zero(1, s);
         {   // Adam's running beta powers start at beta^1 (.pyx:217-218)
@@ -1264,6 +1300,18 @@ extern "C" int mi355rec_mf_get_phase_ticks(mi355rec_mf_t h, uint64_t *out, int64
         if (out && cap > 0) {
             MI_HIP(hipStreamSynchronize(h->stream));
             MI_HIP(hipMemcpy(out, h->ticks.ptr, sizeof(uint64_t) * std::min<size_t>((size_t)cap, h->ticks.count), hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+extern "C" int mi355rec_mf_get_schedule_ticks(mi355rec_mf_t h, uint64_t *out, int64_t cap, int64_t *n) {
+    return guarded([&] {
+        MI_REQUIRE(h && n, "NULL argument");
+        ensure_device();
+        *n = (int64_t)h->sched_ticks.count;
+        if (out && cap > 0) {
+            MI_HIP(hipStreamSynchronize(h->stream));
+            MI_HIP(hipMemcpy(out, h->sched_ticks.ptr, sizeof(uint64_t) * std::min<size_t>((size_t)cap, h->sched_ticks.count), hipMemcpyDeviceToHost));
         }
     });
 }

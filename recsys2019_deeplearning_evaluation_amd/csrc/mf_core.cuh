@@ -142,42 +142,54 @@ template <class T> __device__ __forceinline__ T moved(T w, T lr, T step) {      
     return w + a;
 }
 
-// One thread per sample of one epoch (sampleBPR_Cython .pyx:940-985 / sampleMSE_Cython :878-935).
+// Sample `sid` of the stream (sampleBPR_Cython .pyx:940-985 / sampleMSE_Cython :878-935): a pure function of (seed, sid) and the
+// URM.  ONE text for the stand-alone sampler below and for the in-LDS schedule's workgroups, which draw their own mini-batch
+// (mf_sched_sort_body): the two must produce the same stream.  `third` = the negative item (BPR) or the rating's bits (FunkSVD).
+__device__ __forceinline__ void mf_draw_sample(const bool bpr, const unsigned long long seed, const unsigned long long sid, const int n_users,
+                                               const int n_items, const int *indptr, const int *indices, const float *data,
+                                               const int sample_negatives, const float quota, int &u, int &i, int &third) {
+    unsigned d = 0;
+    int start = 0, n_seen = 0;
+    do {   // users with no interactions or with no negative item are skipped (.pyx:950-958)
+        u = bounded(draw32(seed, sid, d++), n_users);
+        start = indptr[u];
+        n_seen = indptr[u + 1] - start;
+    } while (n_seen == 0 || n_seen == n_items);
+    const int *row = indices + start;
+    if (bpr) {
+        i = row[bounded(draw32(seed, sid, d++), n_seen)];
+        int j;
+        do { j = bounded(draw32(seed, sid, d++), n_items); } while (!profile_lacks(row, n_seen, j));
+        third = j;
+    } else {
+        // .pyx:898: a POSITIVE is drawn with probability `quota` (sic); no quota -> always positive
+        bool positive = true;
+        if (sample_negatives) positive = (float)draw32(seed, sid, d++) * 2.3283064365386963e-10f <= quota;
+        if (positive) {
+            const int at = bounded(draw32(seed, sid, d++), n_seen);
+            i = row[at];
+            third = __float_as_int(data[start + at]);
+        } else {
+            do { i = bounded(draw32(seed, sid, d++), n_items); } while (!profile_lacks(row, n_seen, i));
+            third = __float_as_int(0.f);
+        }
+    }
+}
+
+// One thread per sample of one epoch.
 template <int ALGO, class T>
 __device__ __forceinline__ void mf_sample_body(const MfParams<T> &p) {
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     const long long epoch = p.state->epoch;
     if (t < p.samples_per_epoch) {
         const unsigned long long sid = (unsigned long long)(epoch * p.samples_per_epoch + t);   // global sample id
-        unsigned d = 0;
-        int u, start = 0, n_seen = 0;
-        do {   // users with no interactions or with no negative item are skipped (.pyx:950-958)
-            u = bounded(draw32(p.seed, sid, d++), p.n_users);
-            start = p.indptr[u];
-            n_seen = p.indptr[u + 1] - start;
-        } while (n_seen == 0 || n_seen == p.n_items);
-        const int *row = p.indices + start;
+        int u, i, third;
+        mf_draw_sample(ALGO == MI355REC_MF_BPR, p.seed, sid, p.n_users, p.n_items, p.indptr, p.indices, p.data, p.sample_negatives, p.quota,
+                       u, i, third);
         p.su[t] = u;
-        if (ALGO == MI355REC_MF_BPR) {
-            p.si[t] = row[bounded(draw32(p.seed, sid, d++), n_seen)];
-            int j;
-            do { j = bounded(draw32(p.seed, sid, d++), p.n_items); } while (!profile_lacks(row, n_seen, j));
-            p.sj[t] = j;
-        } else {
-            // .pyx:898: a POSITIVE is drawn with probability `quota` (sic); no quota -> always positive
-            bool positive = true;
-            if (p.sample_negatives) positive = (float)draw32(p.seed, sid, d++) * 2.3283064365386963e-10f <= p.quota;
-            if (positive) {
-                const int at = bounded(draw32(p.seed, sid, d++), n_seen);
-                p.si[t] = row[at];
-                p.sr[t] = p.data[start + at];
-            } else {
-                int i;
-                do { i = bounded(draw32(p.seed, sid, d++), p.n_items); } while (!profile_lacks(row, n_seen, i));
-                p.si[t] = i;
-                p.sr[t] = 0.f;
-            }
-        }
+        p.si[t] = i;
+        if (ALGO == MI355REC_MF_BPR) p.sj[t] = third;
+        else p.sr[t] = __int_as_float(third);
     }
     // (the epoch counter is advanced by the NEXT kernel on the stream, mf_epoch_advance_kernel: a grid larger than the device's
     // residency -- FunkSVD draws 20 M samples per epoch -- still has blocks to start when the first ones retire, and they must

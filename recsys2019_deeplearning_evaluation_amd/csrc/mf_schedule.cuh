@@ -132,6 +132,10 @@ constexpr int META_WIDE = 1 << 30;        // header.meta: bits 0-27 list length,
 constexpr int SCHED_THREADS = 1024;
 constexpr int SLOT_ABSORBED = 0x3fffffff;   // qtask[] of an incidence whose row is updated by its sample's user task (no header of its own)
 constexpr int FAST_MAX_BATCHES = 256, FAST_MAX_SLOTS = 8192;
+// qtask[] of every other incidence: bits 0-12 the header slot (< FAST_MAX_SLOTS), bits 13-17 the incidence's offset within its run
+// (saturated: the emit kernel asks for offsets 0 .. 4 * group - 1 <= 15 only), bit 29 the run is the first of a pair task, bit 30 wide
+constexpr int QTASK_SLOT_MASK = FAST_MAX_SLOTS - 1, QTASK_OFF_SHIFT = 13, QTASK_OFF_MAX = 31, QTASK_PAIR = 1 << 29;
+constexpr int SCHED_STAMPS = 8;           // per workgroup of the sort kernel: entry, keys, sort, run heads, once-touched flags, slot scans, headers, exit
 
 struct FastSchedParams {
     long long n_samples;
@@ -141,8 +145,20 @@ struct FastSchedParams {
     int mid_bytes;                // LDS bytes between the keys and the once-touched flags (run starts + header slots, or the sort's scratch)
     int entry_bits;               // bits of a row id (users, then items) + 1: the padding keys' all-ones field sorts last
     int fuse;                     // BPR: a sample whose user row is touched once in the batch takes over its other once-touched rows
-    const int *su, *si, *sj;
-    const float *sr;
+    int *su, *si, *sj;
+    float *sr;
+    // draw = 1: the sort kernel's workgroups DRAW their mini-batch (mf_draw_sample: sample t of epoch e is a pure function of seed, e
+    // and t) and store it to su/si/sj/sr, instead of reading back what a sampler launch in front of them wrote; the finish kernel
+    // then advances the epoch counter (advance_epoch = 1) -- never a kernel that reads it, whose later workgroups would see the next
+    // epoch.  Zero for replayed streams, schedule parts of a long stream, the group and the exact multi-GPU mode.
+    int draw, advance_epoch, bpr, sample_negatives, n_items;
+    float quota;
+    unsigned long long seed;
+    long long samples_per_epoch, first_sample;      // first_sample: index within the epoch of su[0]
+    MfState *state;
+    const int *indptr, *indices;
+    const float *data;
+    unsigned long long *ticks;    // optional [n_batches][SCHED_STAMPS] shader-clock stamps of the sort kernel's phases (thread 0 of every workgroup)
     unsigned *touched;            // [n_entries][words]: bit b of row x = mini-batch b of this stream touches x
     unsigned char *par;           // [n_entries]: buffer of every row's current version at stream start
     int *sorted_slot;             // [n_batches][tasks_per_batch]: per batch-local incidence (sample * per + role) its position in (row, id) order | also << 16
@@ -186,17 +202,42 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     const long long first = (long long)b * s.batch_size;
     const int n_in = (int)min((long long)s.batch_size, s.n_samples - first);
     const int m = n_in * s.per;
-    for (int q = tid; q < np; q += SCHED_THREADS) {
-        unsigned key = 0xFFFFFFFFu;
-        if (q < m) {
-            const int smp = q / s.per, role = q - smp * s.per;
+    auto mark = [&](int phase) {                   // (s.ticks is NULL unless stamps were asked for: a scalar branch, no stamp executes)
+        if (s.ticks && tid == 0) s.ticks[(size_t)b * SCHED_STAMPS + phase] = stamp();
+    };
+    mark(0);
+    if (s.draw) {
+        // the workgroup draws its own mini-batch: the keys come from registers, the stream is stored for the emit kernel,
+        // last_epoch_samples() and the oracle replay (the epoch word is read here and advanced by the finish kernel)
+        const unsigned long long sid0 = (unsigned long long)(s.state->epoch * s.samples_per_epoch + s.first_sample + first);
+        for (int smp = tid; smp < n_in; smp += SCHED_THREADS) {
+            int u, i, third;
+            mf_draw_sample(s.bpr != 0, s.seed, sid0 + (unsigned long long)smp, s.n_users, s.n_items, s.indptr, s.indices, s.data,
+                           s.sample_negatives, s.quota, u, i, third);
             const long long t = first + smp;
-            const int entry = role == 0 ? s.su[t] : s.n_users + (role == 1 ? s.si[t] : s.sj[t]);
-            key = ((unsigned)entry << sb) | (unsigned)q;
+            s.su[t] = u;
+            s.si[t] = i;
+            if (s.bpr) s.sj[t] = third; else s.sr[t] = __int_as_float(third);
+            const int q = smp * s.per;
+            K[q] = ((unsigned)u << sb) | (unsigned)q;
+            K[q + 1] = ((unsigned)(s.n_users + i) << sb) | (unsigned)(q + 1);
+            if (s.per == 3) K[q + 2] = ((unsigned)(s.n_users + third) << sb) | (unsigned)(q + 2);
         }
-        K[q] = key;
+        for (int q = m + tid; q < np; q += SCHED_THREADS) K[q] = 0xFFFFFFFFu;
+    } else {
+        for (int q = tid; q < np; q += SCHED_THREADS) {
+            unsigned key = 0xFFFFFFFFu;
+            if (q < m) {
+                const int smp = q / s.per, role = q - smp * s.per;
+                const long long t = first + smp;
+                const int entry = role == 0 ? s.su[t] : s.n_users + (role == 1 ? s.si[t] : s.sj[t]);
+                key = ((unsigned)entry << sb) | (unsigned)q;
+            }
+            K[q] = key;
+        }
     }
     __syncthreads();
+    mark(1);
     // (the sort's scratch lives where the run starts / header slots go afterwards)
     switch (np / SCHED_THREADS) {
         case 1: SchedSort<1>::run(K, hpos, sb, sb + s.entry_bits); break;
@@ -205,6 +246,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         default: SchedSort<8>::run(K, hpos, sb, sb + s.entry_bits); break;
     }
     __syncthreads();
+    mark(2);
     // run heads -> hpos[]
     const int C = np / SCHED_THREADS;
     int cnt = 0;
@@ -220,6 +262,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     }
     if (tid == 0) hpos[total] = m;
     __syncthreads();
+    mark(3);
     // FUSED SAMPLE TASKS (BPR).  Most rows of a mini-batch are touched by exactly one sample (users nearly always, uniformly drawn
     // negative items mostly): as separate tasks each of them gathers the sample's three rows again -- nine row reads and three
     // wavefronts per sample.  A sample whose USER row is touched once keeps one task (the user's) which also applies the update of
@@ -254,6 +297,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
             if (!lone_user(q0 + e)) return false;
         return true;
     };
+    mark(4);
     // header slots: wide tasks first (4 aligned slots each), then the others; both in row order
     const int CT = (total + SCHED_THREADS - 1) / SCHED_THREADS;
     const int t_lo = min(tid * CT, total), t_hi = min(t_lo + CT, total);
@@ -268,6 +312,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     Scan().exclusive_scan(wcnt, woff, 0, n_wide, scan_tmp);
     __syncthreads();
     Scan().exclusive_scan(acnt, aoff, 0, n_abs, scan_tmp);
+    mark(5);
     TaskHeader *out = s.tasks + (size_t)b * s.tasks_per_batch;
     for (int t = t_lo; t < t_hi; ++t) {
         const int start = hpos[t], len = hpos[t + 1] - start;
@@ -282,7 +327,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         }
         const int slot = wide ? 4 * woff : 4 * n_wide + (t - woff - aoff);
         woff += wide;
-        tpos[t] = slot | (wide ? META_WIDE : 0);
+        tpos[t] = slot | (wide ? META_WIDE : 0) | (pair ? QTASK_PAIR : 0);
         for (int part = 0; part < (wide ? 4 : 1); ++part) {
             *reinterpret_cast<int4 *>(out + slot + part) =
                 make_int4(entry, (pair ? s.group : len) | (wide ? META_WIDE | (part << 28) : 0), b * s.tasks_per_batch + start, pair ? 1 : 0);
@@ -295,6 +340,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     for (int slot = used + tid; slot < fill_end; slot += SCHED_THREADS)
         *reinterpret_cast<int4 *>(out + slot) = make_int4(0, 0, 0, 0);          // no samples: the slot's wavefront idles
     __syncthreads();
+    mark(6);
     for (int q = tid; q < m; q += SCHED_THREADS) {
         int lo = 0, hi = total;                       // last run starting at or before q
         while (hi - lo > 1) {
@@ -310,22 +356,42 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         // (by INCIDENCE: the emit kernel runs one thread per sample, which looks its three incidences' sorted positions up; a scattered
         // 4-byte store into the mini-batch's 12 KB here, three coalesced loads there)
         s.sorted_slot[(size_t)b * s.tasks_per_batch + inc] = q | (also << 16);
-        s.qtask[(size_t)b * s.tasks_per_batch + q] = tpos[lo];
+        // (the emit kernel learns where in its run the incidence sits from here, not from the header's `start`: one dependent trip less)
+        const int tp = tpos[lo];
+        s.qtask[(size_t)b * s.tasks_per_batch + q] = tp == SLOT_ABSORBED ? tp : tp | (min(q - hpos[lo], QTASK_OFF_MAX) << QTASK_OFF_SHIFT);
     }
+    mark(7);
 }
 __global__ __launch_bounds__(SCHED_THREADS) void mf_sched_sort_kernel(const FastSchedParams s) { mf_sched_sort_body(s, blockIdx.x); }
 
-__device__ __forceinline__ int version_parity(const FastSchedParams &s, int entry, int b) {
-    const unsigned *w = s.touched + (size_t)entry * s.words;
+// A row's bitmap of the stream's mini-batches: FAST_MAX_BATCHES bits = 32 aligned bytes, fetched as two 16-byte loads.
+struct RowBits { uint4 lo, hi; };
+__device__ __forceinline__ RowBits row_bits(const FastSchedParams &s, int entry) {
+    const uint4 *w = reinterpret_cast<const uint4 *>(s.touched + (size_t)entry * (FAST_MAX_BATCHES / 32));
+    RowBits r;
+    r.lo = w[0];
+    r.hi = w[1];
+    return r;
+}
+// buffer of the row's version that mini-batch b reads = parity at stream start + number of earlier mini-batches that touch the row
+__device__ __forceinline__ int version_parity(const RowBits &r, int par, int b) {
+    const unsigned w[8] = {r.lo.x, r.lo.y, r.lo.z, r.lo.w, r.hi.x, r.hi.y, r.hi.z, r.hi.w};
     int cnt = 0;
-    for (int k = 0; k < (b >> 5); ++k) cnt += __popc(w[k]);
-    cnt += __popc(w[b >> 5] & ((1u << (b & 31)) - 1u));
-    return (s.par[entry] + cnt) & 1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {     // (b is the same for the whole workgroup: the masks are scalars)
+        const unsigned mask = k < (b >> 5) ? 0xFFFFFFFFu : (k == (b >> 5) ? (1u << (b & 31)) - 1u : 0u);
+        cnt += __popc(w[k] & mask);
+    }
+    return (par + cnt) & 1;
 }
 
 // One thread per SAMPLE (until round 6: per incidence -- every sample's ids were then fetched by three threads at three unrelated
 // sorted positions and the version parities of its three rows evaluated three times over: 1.08 GB fetched per 32-model epoch).  The
 // sample's ids come in coalesced, each row's parity is evaluated once, and the record goes to the sample's three sorted positions.
+// Two dependent trips: (1) the sample's ids and its incidences' sorted positions; (2) everything they address, requested at once --
+// the three rows' bitmaps and start parities, the incidences' qtask words and those of their aligned blocks' first positions.  The
+// qtask word carries what used to be read from the header (offset within the run, "first of a pair task"); only the own-row
+// buffer bit of a run's first incidence still costs a third trip, the header's meta word.
 __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
     const int b = blockIdx.y, smp = blockIdx.x * 256 + threadIdx.x;
     const long long first = (long long)b * s.batch_size;
@@ -333,13 +399,28 @@ __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
     if (smp >= n_in) return;
     const size_t base = (size_t)b * s.tasks_per_batch;
     const long long t = first + smp;
-    const int u = s.su[t], i = s.si[t], j = s.per == 3 ? s.sj[t] : 0;
-    const int third = s.per == 3 ? j : __float_as_int(s.sr[t]);
+    // (straight-line on purpose: a branch on `per` around a load makes the compiler wait for the loads in front of it.  Both
+    // algorithms own all four stream buffers; a role the algorithm does not have repeats role 0 and is dropped below.)
+    const bool three = s.per == 3;
+    const int u = s.su[t], i = s.si[t], j = s.sj[t];
+    const int rating = __float_as_int(s.sr[t]);
     int where[3];
 #pragma unroll
-    for (int role = 0; role < 3; ++role) where[role] = role < s.per ? s.sorted_slot[base + (size_t)smp * s.per + role] : 0;
-    const int pu = version_parity(s, u, b), pi = version_parity(s, s.n_users + i, b);
-    const int pj = s.per == 3 ? version_parity(s, s.n_users + j, b) : 0;
+    for (int role = 0; role < 3; ++role) where[role] = s.sorted_slot[base + (size_t)smp * s.per + (role < s.per ? role : 0)];
+    const int third = three ? j : rating;
+    const int ej = s.n_users + (three ? j : i);          // (FunkSVD: no third row; the item's again, unused)
+    const RowBits bu = row_bits(s, u), bi = row_bits(s, s.n_users + i), bj = row_bits(s, ej);
+    const int su0 = s.par[u], si0 = s.par[s.n_users + i], sj0 = s.par[ej];
+    const int gmask = s.group - 1, gshift = s.group >> 1;       // group is 1, 2 or 4 (samples_in_flight)
+    int tps[3], tps0[3];
+#pragma unroll
+    for (int role = 0; role < 3; ++role) {
+        const int q = where[role] & 0xffff;
+        tps[role] = s.qtask[base + q];
+        tps0[role] = s.qtask[base + (q & ~gmask)];
+    }
+    const int pu = version_parity(bu, su0, b), pi = version_parity(bi, si0, b);
+    const int pj = three ? version_parity(bj, sj0, b) : 0;
     const int par_bits = (pu << 2) | (pi << 3) | (pj << 4);
 #pragma unroll
     for (int role = 0; role < 3; ++role) {
@@ -348,32 +429,29 @@ __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
         const size_t at = base + q;
         const int4 rec = make_int4(u, i, third, role | par_bits | (also << 5));
         s.recs[at] = rec;
-        const int tp = s.qtask[at];
+        const int tp = tps[role];
         if (tp == SLOT_ABSORBED) {
             // a sample of a PAIR task other than its first (pairs are aligned blocks of `group` sorted positions, the header belongs to the
             // first): its record also goes where the mini-batch kernel finds it without having seen the header -- by header slot
-            const int q0 = q - q % s.group;
-            if (s.fuse && q0 != q) {
-                const int tp0 = s.qtask[base + q0];
-                if (tp0 != SLOT_ABSORBED && !(tp0 & META_WIDE)) {
-                    const TaskHeader *lead = s.tasks + base + tp0;
-                    if (lead->pad == 1 && lead->start == (int)(base + q0)) s.slot_recs[(base + tp0) * 3 + (q - q0 - 1)] = rec;
-                }
-            }
+            const int q0 = q & ~gmask, tp0 = tps0[role];
+            if (s.fuse && q0 != q && tp0 != SLOT_ABSORBED && (tp0 & QTASK_PAIR))
+                s.slot_recs[(base + (tp0 & QTASK_SLOT_MASK)) * 3 + (q - q0 - 1)] = rec;
             continue;
         }
-        TaskHeader *hd = s.tasks + base + (tp & (META_WIDE - 1));
-        const int off = (int)(at - (size_t)hd->start);
+        TaskHeader *hd = s.tasks + base + (tp & QTASK_SLOT_MASK);
+        const int off = (tp >> QTASK_OFF_SHIFT) & QTASK_OFF_MAX;      // (saturated at QTASK_OFF_MAX, past every offset asked for below)
         const int own = role == 0 ? pu : (role == 1 ? pi : pj);
         int part = -1;
         if (tp & META_WIDE) {           // quarter k of a wide list starts at position k * group
-            if (off % s.group == 0 && off / s.group < 4) part = off / s.group;      // (quarters past the end of the list stay empty)
+            if ((off & gmask) == 0 && (off >> gshift) < 4) part = off >> gshift;      // (quarters past the end of the list stay empty)
         } else if (off == 0) {
             part = 0;
         }
         if (part >= 0) {
             hd[part].rec0 = rec;
-            hd[part].meta |= own << 31;
+            // (the sort kernel left the bit clear.  An atomic OR without a return value was measured instead of this read-modify-
+            // write of the one thread that owns the header: 66 k device-scope atomics per epoch made the kernel 4 us slower)
+            if (own) hd[part].meta |= (int)(1u << 31);
         }
     }
 }
@@ -382,6 +460,8 @@ __global__ __launch_bounds__(256) void mf_sched_emit_kernel(const FastSchedParam
 
 __device__ __forceinline__ void mf_sched_finish_body(const FastSchedParams &s) {
     const int x = blockIdx.x * 256 + threadIdx.x;
+    // the epoch the sort kernel's workgroups drew is done with: every one of them has retired (this is the launch after the next)
+    if (s.advance_epoch && x == 0) s.state->epoch += 1;
     if (x >= s.n_entries) return;
     unsigned *w = s.touched + (size_t)x * s.words;
     int cnt = 0;
