@@ -61,7 +61,9 @@ class MatrixFactorization_MI355X_Epoch(N.Handle):
         self.use_bias = bool(use_bias)
         self.verbose = verbose
         if random_seed is not None:
-            np.random.seed(seed=random_seed)
+            # the device stream takes a 64-bit seed; NumPy's legacy generator takes 32-bit words, so a seed of 2^32 and above is
+            # handed over as its two words (it was refused with a ValueError) -- below 2^32 the initial factors are what they were
+            np.random.seed(seed=random_seed if int(random_seed) < 2 ** 32 else [int(random_seed) & 0xFFFFFFFF, int(random_seed) >> 32])
         # same draw order as .pyx:174-175; an explicit initial model (parity tests) overrides the draw.  AsySVD keeps two
         # item-sized matrices (.pyx:163-166): its "USER_factors" is the n_items x k matrix Y
         self.n_user_rows = self.n_items if algorithm_name == "ASY_SVD" else self.n_users
