@@ -428,7 +428,9 @@ void mi355rec_ials_destroy(mi355rec_ials_t h);
 typedef struct mi355rec_slimen *mi355rec_slimen_t;
 
 /* URM_train (n_users x n_items) in both layouts, CSR and CSC, float32 values, sorted indices.  Builds G = X^T X (n_items^2 float32,
- * never leaves the device) and diag = column sums of squares; fails with MI355REC_E_INVALID when G does not fit the free memory. */
+ * kept on the device; the fits read it there and mi355rec_slimen_get_gram copies rows of it out) and diag = column sums of squares;
+ * fails with MI355REC_E_INVALID when G does not fit the free memory.  Row j of G is accumulated in LDS up to 40 960 items and by global
+ * atomics into the row itself beyond; MI355REC_SLIMEN_GLOBAL_GRAM=1 forces the latter at any size (tests). */
 int mi355rec_slimen_create(mi355rec_slimen_t *out, int32_t n_users, int32_t n_items, const int32_t *row_ptr, const int32_t *row_idx,
                            const float *row_val, const int32_t *col_ptr, const int32_t *col_idx, const float *col_val);
 /* Fits the targets [start_item, end_item): seeds[t] is the solver seed of target start_item + t (np.random.randint(0, 2**31 - 1),
@@ -441,11 +443,14 @@ int mi355rec_slimen_fit(mi355rec_slimen_t h, int32_t start_item, int32_t end_ite
  * n_iter[t] sweeps run, converged[t] = 1 when the duality gap fell below tol * y.y.  slots_per_target = max(1, min(topK, n_items - 1)), n_items - 1 for topK = -1. */
 int mi355rec_slimen_get(mi355rec_slimen_t h, int32_t *counts, int32_t *n_iter, int32_t *converged, int32_t *rows, float *values,
                         int32_t slots_per_target);
+/* Rows [row0, row1) of G, row-major (row1 - row0) x n_items, into rows; diag (may be NULL) receives diag[row0:row1] (tests). */
+int mi355rec_slimen_get_gram(mi355rec_slimen_t h, int32_t row0, int32_t row1, float *rows, float *diag);
 int mi355rec_slimen_get_stats(mi355rec_slimen_t h, mi355rec_stats *stats);
 /* Counters of the last fit: accepted coordinate changes (= rows of G streamed), sweeps, block steps (windows of draws), duality-gap
- * tests; h_in_lds = 1 when H was kept in LDS; gram_ms = device time of the Gram build of the create call. */
+ * tests; h_in_lds = 1 when H was kept in LDS; gram_in_lds = 1 when the create call accumulated the rows of G in LDS; gram_ms = device
+ * time of the Gram build of the create call. */
 int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, int64_t *sweeps, int64_t *steps, int64_t *gap_tests,
-                             int32_t *h_in_lds, double *gram_ms);
+                             int32_t *h_in_lds, int32_t *gram_in_lds, double *gram_ms);
 void mi355rec_slimen_destroy(mi355rec_slimen_t h);
 
 /* ------------------------------------------------------------------------------------------------------

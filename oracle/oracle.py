@@ -12,6 +12,9 @@ surface of the reference object it restates so that tests read like the referenc
   OracleSLIM    <- SLIM_BPR_Cython_Epoch              (SLIM_BPR/Cython/SLIM_BPR_Cython_Epoch.pyx:59; dense + symmetric stores)
   OracleSimilarity <- Compute_Similarity_Cython       (Base/Similarity/Cython/Compute_Similarity_Cython.pyx:51)
   oracle_ials_epoch / OracleIALS <- IALSRecommender   (MatrixFactorization/IALSRecommender.py:137-210)
+  slimen_replay <- sklearn's sparse_enet_coordinate_descent as SLIMElasticNetRecommender runs it (SLIM_ElasticNet/
+                   SLIMElasticNetRecommender.py:41-149), in Gram form; pinned to the reference's fits through
+                   tests/slim_elasticnet_cases.py replay_target (tests/test_slim_elasticnet_spec.py)
   oracle_similarity_topk_rows <- similarityMatrixTopK / Triangular_Matrix.get_scipy_csr (Base/Recommender_utils.py:55,
                                                         SLIM_BPR_Cython_Epoch.pyx:1338-1418)
 
@@ -93,12 +96,49 @@ def lib():
                                      + [C.c_double] * 2 + [_p] * 3)
         L.orc_sim_build.argtypes = ([C.c_int32] * 4 + [_p] * 7 + [C.c_int32] * 3 + [_p] * 3
                                     + [C.c_double] * 2 + [_p] * 2)
+        L.orc_slimen_replay.argtypes = ([C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double]
+                                        + [_p] * 14)
         _lib = L
     return _lib
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def slimen_replay(j, seed, l1, l2, positive, diag, G=None, X=None, max_iter=100, tol=1e-4, single=False):
+    """orc_slimen_replay: float64 coordinate descent of SLIM ElasticNet's target j in Gram form, one draw at a time.  G: the Gram
+    matrix (dense or sparse), or None with X the URM, whose Gram columns are then formed on demand (no n_items^2 storage).
+    `_slimen_operands` prepares either once for many targets.  single: the float32 host model (every operation of the update rounded
+    to float32; the operands, l1, l2 and tol are rounded here, prepared operands must have been made with single=True).
+    Returns (w, n_iter, converged, accepted changes), w in float64 (holding float32 values when single)."""
+    ops = G if isinstance(G, _SlimenOperands) else _slimen_operands(G, X, single)
+    assert ops.single == bool(single)
+    diag = np.ascontiguousarray(diag, dtype=np.float64)
+    if single:
+        diag, l1, l2, tol = diag.astype(np.float32).astype(np.float64), np.float32(l1), np.float32(l2), np.float32(tol)
+    w = np.zeros(ops.n, np.float64)
+    n_iter, conv, changes = C.c_int32(), C.c_int32(), C.c_int64()
+    lib().orc_slimen_replay(int(bool(single)), ops.n, int(j), int(seed), float(l1), float(l2), int(bool(positive)), int(max_iter), float(tol),
+                            *[_ptr(a) for a in ops.arrays], _ptr(diag), _ptr(w), C.addressof(n_iter), C.addressof(conv), C.addressof(changes))
+    return w, n_iter.value, bool(conv.value), changes.value
+
+
+class _SlimenOperands:
+    def __init__(self, n, arrays, single):
+        self.n, self.arrays, self.single = n, arrays, bool(single)
+
+
+def _slimen_operands(G=None, X=None, single=False):
+    def parts(M):
+        M.sort_indices()
+        data = M.data.astype(np.float32) if single else M.data
+        return [np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.int32),
+                np.ascontiguousarray(data, dtype=np.float64)]
+    if G is not None:
+        G = sps.csc_matrix(G, dtype=np.float64)
+        return _SlimenOperands(G.shape[0], parts(G) + [None] * 6, single)
+    return _SlimenOperands(X.shape[1], [None] * 3 + parts(sps.csr_matrix(X, dtype=np.float64)) + parts(sps.csc_matrix(X, dtype=np.float64)), single)
 
 
 def _sorted_csr(URM):

@@ -153,7 +153,8 @@ SIGNATURES = {
     "mi355rec_slimen_get": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "mi355rec_slimen_get_stats": (C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_slimen_fit_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32),
-                                           C.POINTER(_f64)]),
+                                           C.POINTER(_i32), C.POINTER(_f64)]),
+    "mi355rec_slimen_get_gram": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "mi355rec_slimen_destroy": (None, [_vp]),
     "mi355rec_svd_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355rec_svd_set_block": (C.c_int, [_vp, _i32, _vp]),

@@ -11,7 +11,8 @@
 // Kernels
 //   slimen_diag_kernel   d_k = sum_u X_uk^2 in the column's stored order (the reference's norm_cols_X, fp32);
 //   slimen_gram_kernel   G row by row, one workgroup per item: sum over the users of item j of x_uj * X[u, :], accumulated in LDS
-//                        (float atomics: exact for integer / quantised values) or, beyond the LDS, in the row of G itself;
+//                        (float atomics: exact for integer / quantised values) or, beyond the LDS or with
+//                        MI355REC_SLIMEN_GLOBAL_GRAM=1, in the row of G itself;
 //   slimen_fit_kernel    a persistent grid, one target per workgroup, targets taken from a queue word by a vector atomic.  H lives in
 //                        LDS (H_LDS) or in a per-workgroup global slot; w lives in a per-workgroup global slot behind a nonzero
 //                        bitmask in LDS (w is read only where the bit is set, so a slot is never cleared).
@@ -433,7 +434,7 @@ struct mi355rec_slimen : Handle {                     // `timer`: the fit kernel
     DeviceBuffer<uint32_t> seeds, jump;
     DeviceBuffer<unsigned> queue;
     DeviceBuffer<unsigned long long> counters;
-    int n_targets = 0, slots_per_target = 0, h_in_lds = 0;
+    int n_targets = 0, slots_per_target = 0, h_in_lds = 0, gram_in_lds = 0;
     double gram_ms = 0.0;
     unsigned long long counts[4] = {0, 0, 0, 0};
 
@@ -473,7 +474,9 @@ extern "C" int mi355rec_slimen_create(mi355rec_slimen_t *out, int32_t n_users, i
         hipLaunchKernelGGL(slimen_diag_kernel, dim3(div_up(n_items, 256)), dim3(256), 0, s, cp.ptr, cv.ptr, n_items, h->diag.ptr);
         MI_HIP(hipGetLastError());
         const size_t acc_lds = (size_t)n_items * sizeof(float);
-        if (acc_lds <= LDS_LIMIT) {
+        const char *force = getenv("MI355REC_SLIMEN_GLOBAL_GRAM");
+        h->gram_in_lds = acc_lds <= LDS_LIMIT && !(force && atoi(force));
+        if (h->gram_in_lds) {
             auto k = slimen_gram_kernel<true>;
             MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_lds));
             hipLaunchKernelGGL(k, dim3(n_items), dim3(GRAM_THREADS), acc_lds, s, rp.ptr, ri.ptr, rv.ptr, cp.ptr, ci.ptr, cv.ptr, n_items,
@@ -597,17 +600,32 @@ extern "C" int mi355rec_slimen_get(mi355rec_slimen_t h, int32_t *counts, int32_t
     });
 }
 
+extern "C" int mi355rec_slimen_get_gram(mi355rec_slimen_t h, int32_t row0, int32_t row1, float *rows, float *diag) {
+    return guarded([&] {
+        MI_REQUIRE(h && rows, "NULL argument");
+        MI_REQUIRE(0 <= row0 && row0 <= row1 && row1 <= h->n_items, "row range [%d, %d) outside [0, %d)", row0, row1, h->n_items);
+        ensure_device();
+        ReleaseScope scope(h->stream);
+        const size_t N = (size_t)h->n_items, n = (size_t)(row1 - row0);
+        if (n == 0) return;
+        MI_HIP(hipMemcpyAsync(rows, h->G.ptr + (size_t)row0 * N, n * N * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (diag) MI_HIP(hipMemcpyAsync(diag, h->diag.ptr + row0, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        MI_HIP(hipStreamSynchronize(h->stream));
+    });
+}
+
 extern "C" int mi355rec_slimen_get_stats(mi355rec_slimen_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }
 
 extern "C" int mi355rec_slimen_fit_info(mi355rec_slimen_t h, int64_t *changes, int64_t *sweeps, int64_t *steps, int64_t *gap_tests,
-                                        int32_t *h_in_lds, double *gram_ms) {
+                                        int32_t *h_in_lds, int32_t *gram_in_lds, double *gram_ms) {
     return guarded([&] {
-        MI_REQUIRE(h && changes && sweeps && steps && gap_tests && h_in_lds && gram_ms, "NULL argument");
+        MI_REQUIRE(h && changes && sweeps && steps && gap_tests && h_in_lds && gram_in_lds && gram_ms, "NULL argument");
         *changes = (int64_t)h->counts[0];
         *sweeps = (int64_t)h->counts[1];
         *steps = (int64_t)h->counts[2];
         *gap_tests = (int64_t)h->counts[3];
         *h_in_lds = h->h_in_lds;
+        *gram_in_lds = h->gram_in_lds;
         *gram_ms = h->gram_ms;
     });
 }

@@ -65,10 +65,16 @@ class SLIMElasticNet_MI355X_Fit(N.Handle):
 
     def fit_info(self):
         v = [C.c_int64() for _ in range(4)]
-        lds, gram_ms = C.c_int32(), C.c_double()
-        self._call("fit_info", *[C.byref(x) for x in v], C.byref(lds), C.byref(gram_ms))
+        lds, gram_lds, gram_ms = C.c_int32(), C.c_int32(), C.c_double()
+        self._call("fit_info", *[C.byref(x) for x in v], C.byref(lds), C.byref(gram_lds), C.byref(gram_ms))
         return {"changes": v[0].value, "sweeps": v[1].value, "steps": v[2].value, "gap_tests": v[3].value, "h_in_lds": bool(lds.value),
-                "gram_ms": gram_ms.value}
+                "gram_in_lds": bool(gram_lds.value), "gram_ms": gram_ms.value}
+
+    def gram_rows(self, row0, row1):
+        """Rows [row0, row1) of the device's G = X^T X and diag[row0:row1] (tests: G is otherwise only read by the fits)."""
+        rows, diag = np.zeros((row1 - row0, self.n_items), np.float32), np.zeros(row1 - row0, np.float32)
+        self._call("get_gram", int(row0), int(row1), N.ptr(rows), N.ptr(diag))
+        return rows, diag
 
 
 def slots_to_csr(rows, values, counts, start, n_items):
