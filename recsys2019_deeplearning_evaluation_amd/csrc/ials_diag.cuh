@@ -5,10 +5,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ials_tile.h"                   // TP
+
 namespace mi355rec {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-constexpr int TP = 17;                   // padded row length of a 16 x 16 tile staged in LDS (conflict-free operand reads)
 
 __device__ __forceinline__ double lane_bcast(double v, int src_lane) {
     const long long b = __builtin_bit_cast(long long, v);
