@@ -44,8 +44,10 @@
 
 #include <memory>
 
-// One translation unit, split by stage (round 4): the device code lives in the four headers below (parameters + optimiser step +
-// sampler | schedules | mini-batch kernels | AsySVD), this file holds the handles, kernel selection, graphs and the C ABI.
+// One translation unit, split by stage: mf_plan.h holds every decision as host-only arithmetic on plain numbers (and the constants the
+// kernels share with it), the four .cuh headers the device code (parameters + optimiser step + sampler | schedules | mini-batch
+// kernels | AsySVD); this file holds the handles, the launches, the graphs and the C ABI.
+#include "mf_plan.h"
 #include "mf_core.cuh"
 #include "mf_schedule.cuh"
 #include "mf_batch.cuh"
@@ -60,75 +62,121 @@ struct mi355rec_mf : Handle {
     int n_u_rows = 0;                 // rows of U: n_users, or n_items for AsySVD
     bool f64 = false;                 // storage / arithmetic type of factors and moments
     size_t nnz = 0;
-    DeviceBuffer<int> indptr, indices, su, si, sj;
-    DeviceBuffer<float> data, sr, stage;
+    DeviceBuffer<int> indptr, indices;
+    DeviceBuffer<float> data, stage;
     // T-typed arrays (float or double by `f64`), held as bytes
     DeviceBuffer<unsigned char> U[2], V[2], bu[2], bi[2], c1U, c2U, c1V, c2V, c1_bu, c2_bu, c1_bi, c2_bi;
     DeviceBuffer<unsigned char> mu_state, mu_acc, asy_mu, asy_c_mu;
     DeviceBuffer<unsigned char> par;
     DeviceBuffer<double> loss_slots;
     DeviceBuffer<MfState> state;
-    // schedule
-    DeviceBuffer<unsigned long long> keys, keys_sorted;
-    DeviceBuffer<int> slots, slots_sorted, head, head_scan, task_at, batch_count;
-    DeviceBuffer<unsigned char> spar, cub_tmp;
-    DeviceBuffer<TaskHeader> tasks;
-    DeviceBuffer<unsigned> touched;         // fast schedule: (row, mini-batch) bitmap
-    DeviceBuffer<int> sorted_slot, qtask, used;
-    bool fast_schedule = false;
-    DeviceBuffer<unsigned long long> ticks, sched_ticks;
-    DeviceBuffer<int4> recs, slot_recs;
-    size_t cub_tmp_bytes = 0;
-    size_t stream_capacity = 0;      // samples
-    long long batch_capacity = 0;    // mini-batches the task arrays can hold
+    DeviceBuffer<unsigned long long> ticks;         // MI355REC_MF_TICKS: the mini-batch kernel's phase stamps
     long long batches_done = 0;      // batches executed since create (device state mirrors this)
     long long last_call_samples = 0; // samples in the stream buffer after the last native call
     int max_timed = 0;
-    // exact multi-GPU mode: this rank's share of every mini-batch and the exchange slabs
-    DeviceBuffer<unsigned char> shard_send, shard_recv;
-    int shard_rank = -1, shard_world = 0, shard_slots_per_rank = 0;
-    long long shard_batches = 0;
-    // one native epoch: sampler, schedule, n_batches mini-batch kernels -- in graphs of up to GRAPH_SEGMENT mini-batches each
-    std::vector<hipGraphExec_t> epoch_graphs;
-    size_t general_capacity = 0;            // samples the radix-sort schedule's buffers hold
-    bool graph_failed = false;
     std::vector<double> host_loss;
 
+    // the sample stream and what every schedule makes of it: task headers and records (sized by BufferPlan)
+    struct StreamBuffers {
+        DeviceBuffer<int> su, si, sj;
+        DeviceBuffer<float> sr;
+        DeviceBuffer<TaskHeader> tasks;
+        DeviceBuffer<int4> recs, slot_recs;
+        size_t capacity = 0;             // samples
+        long long batch_capacity = 0;    // mini-batches the task arrays can hold
+    } buf;
+    // the radix-sort schedule of a whole stream
+    struct RadixSchedule {
+        DeviceBuffer<unsigned long long> keys, keys_sorted;
+        DeviceBuffer<int> slots, slots_sorted, head, head_scan, task_at, batch_count;
+        DeviceBuffer<unsigned char> spar, cub_tmp;
+        size_t cub_tmp_bytes = 0;
+        size_t capacity = 0;             // samples its buffers hold
+    } radix;
+    // the in-LDS schedule
+    struct LdsSchedule {
+        bool fast_schedule = false;              // available to this handle (cached: see MfShape::fast_schedule)
+        DeviceBuffer<unsigned> touched;          // (row, mini-batch) bitmap
+        DeviceBuffer<int> sorted_slot, qtask, used;
+        DeviceBuffer<unsigned long long> ticks;  // MI355REC_MF_TICKS: the sort kernel's phase stamps
+    } lds;
+    // exact multi-GPU mode: this rank's share of every mini-batch and the exchange slabs
+    struct Shard {
+        DeviceBuffer<unsigned char> send, recv;
+        int rank = -1, world = 0, slots_per_rank = 0;
+        long long batches = 0;
+    } shard;
+    // one native epoch: sampler, schedule, n_batches mini-batch kernels -- in graphs of up to GRAPH_SEGMENT mini-batches each
+    struct Graphs {
+        std::vector<hipGraphExec_t> epoch;
+        bool failed = false;
+    } graphs;
+
     void drop_graphs() {
-        for (hipGraphExec_t g : epoch_graphs) (void)hipGraphExecDestroy(g);
-        epoch_graphs.clear();
+        for (hipGraphExec_t g : graphs.epoch) (void)hipGraphExecDestroy(g);
+        graphs.epoch.clear();
     }
     ~mi355rec_mf() { shutdown([&] { drop_graphs(); }); }
 };
 
 namespace {
 
-int bits_for(unsigned long long n_values) {   // bits needed for values 0 .. n_values - 1 (at least 1)
-    int b = 1;
-    while (b < 63 && (1ull << b) < n_values) ++b;
-    return b;
-}
-
-int per_sample(const mi355rec_mf *h) { return h->cfg.algorithm == MI355REC_MF_BPR ? 3 : 2; }
-
-long long batches_per_epoch(const mi355rec_mf *h) {
-    // .pyx:583 (BPR: n_users / B + 1) and :289 (FunkSVD: nnz / B + 1); ASY_SVD: nnz / 1 + 1 single-sample steps (.pyx:397)
-    const long long B = h->cfg.batch_size;
-    return (h->cfg.algorithm == MI355REC_MF_BPR ? (long long)h->n_users / B : (long long)h->nnz / B) + 1;
+// the plain numbers mf_plan.h decides on (taken when needed: a call may set lds.fast_schedule on its way)
+MfShape shape_of(const mi355rec_mf *h) {
+    MfShape s;
+    s.algorithm = h->cfg.algorithm;
+    s.n_users = h->n_users;
+    s.n_items = h->n_items;
+    s.nnz = (long long)h->nnz;
+    s.k = h->k;
+    s.f64 = h->f64;
+    s.batch_size = h->cfg.batch_size;
+    s.sharded = h->shard.rank >= 0;
+    s.fast_schedule = h->lds.fast_schedule;
+    return s;
 }
 
 template <class T> T *as(const DeviceBuffer<unsigned char> &b) { return reinterpret_cast<T *>(b.ptr); }
 
-bool fast_schedule_fits(const mi355rec_mf *h, long long n_batches);
+// One launch: with per-dispatch events when `e0` is set, else the plain (capturable) form.
+template <class... P, class... A>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const A &...args) {
+    if (e0) hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, e0, e1, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
+}
+
+// `enqueue`'s launches on `s` as an executable graph; null on any failure (the error is cleared: plain launches remain correct, only
+// slower)
+template <class F>
+hipGraphExec_t capture_graph(hipStream_t s, F &&enqueue) {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t exec = nullptr;
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        try {
+            enqueue();
+        } catch (...) {
+            (void)hipStreamEndCapture(s, &g);
+            if (g) (void)hipGraphDestroy(g);
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        e = hipStreamEndCapture(s, &g);
+    }
+    if (e == hipSuccess) e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    if (e == hipSuccess) return exec;
+    (void)hipGetLastError();
+    return nullptr;
+}
 
 template <class T>
-void fill_params(mi355rec_mf *h, MfParams<T> &p) {
+void fill_config(const mi355rec_mf *h, MfParams<T> &p) {
     const auto &c = h->cfg;
     p.n_users = h->n_users; p.n_items = h->n_items; p.k = h->k; p.batch_size = c.batch_size;
     p.use_bias = c.use_bias && c.algorithm != MI355REC_MF_BPR;
     p.sgd_mode = c.sgd_mode;
     p.sample_negatives = c.negative_interactions_quota != 0.0;
-    p.tasks_per_batch = per_sample(h) * c.batch_size;
     p.lr = (T)c.learning_rate; p.user_reg = (T)c.user_reg; p.item_reg = (T)c.item_reg; p.bias_reg = (T)c.bias_reg;
     p.positive_reg = (T)c.positive_reg; p.negative_reg = (T)c.negative_reg;
     p.inv_batch = (T)1 / (T)c.batch_size;
@@ -137,6 +185,13 @@ void fill_params(mi355rec_mf *h, MfParams<T> &p) {
     p.one_m_gamma = (T)(1.0 - c.gamma); p.one_m_beta_1 = (T)(1.0 - c.beta_1); p.one_m_beta_2 = (T)(1.0 - c.beta_2);
     p.beta_1_d = c.beta_1; p.beta_2_d = c.beta_2;
     p.seed = c.random_seed;
+}
+
+template <class T>
+void fill_params(mi355rec_mf *h, MfParams<T> &p) {
+    const MfShape s = shape_of(h);
+    fill_config(h, p);
+    p.tasks_per_batch = tasks_per_batch(s);
     p.indptr = h->indptr.ptr; p.indices = h->indices.ptr; p.data = h->data.ptr;
     p.U0 = as<T>(h->U[0]); p.U1 = as<T>(h->U[1]); p.V0 = as<T>(h->V[0]); p.V1 = as<T>(h->V[1]);
     p.bu0 = as<T>(h->bu[0]); p.bu1 = as<T>(h->bu[1]); p.bi0 = as<T>(h->bi[0]); p.bi1 = as<T>(h->bi[1]);
@@ -147,22 +202,18 @@ void fill_params(mi355rec_mf *h, MfParams<T> &p) {
     p.asy_mu = as<T>(h->asy_mu); p.asy_c_mu = as<T>(h->asy_c_mu);
     p.par = h->par.ptr;
     p.loss_slots = h->loss_slots.ptr; p.state = h->state.ptr;
-    p.su = h->su.ptr; p.si = h->si.ptr; p.sj = h->sj.ptr; p.sr = h->sr.ptr;
-    p.samples_per_epoch = batches_per_epoch(h) * (long long)c.batch_size;
-    p.tasks = h->tasks.ptr; p.recs = h->recs.ptr;
-    p.slot_recs = h->slot_recs.ptr;
-    p.slot_rec_stride = h->fast_schedule ? 3ll * per_sample(h) * c.batch_size : 0;      // (see ensure_stream_capacity)
-    // (only the replica-batched launch sizes its grid below the slot count; it runs whole epochs, i.e. batches_per_epoch mini-batches)
-    p.used = h->fast_schedule && fast_schedule_fits(h, batches_per_epoch(h)) ? h->used.ptr : nullptr;
+    p.su = h->buf.su.ptr; p.si = h->buf.si.ptr; p.sj = h->buf.sj.ptr; p.sr = h->buf.sr.ptr;
+    p.samples_per_epoch = batches_per_epoch(s) * (long long)s.batch_size;
+    p.tasks = h->buf.tasks.ptr; p.recs = h->buf.recs.ptr;
+    p.slot_recs = h->buf.slot_recs.ptr;
+    p.slot_rec_stride = slot_rec_stride(s);
+    p.used = nullptr;                       // (only the group's launch reads it: group_member_table)
     p.ticks = h->ticks.ptr;
     p.wg_base = 0;
     p.wg_stride = 1;
 }
 
-// ---- kernel selection -------------------------------------------------------------------------------------------------
-// (Measured and rejected, round 4: rows of 17 .. 32 chunks on 16 lanes with two chunks each instead of 32 lanes with one -- four samples
-// per wavefront, twice the bytes in flight per wavefront: the row gathers of a wavefront took 3 840 cycles instead of 2 350, one model
-// 140 M samples/s instead of 176 M, the 32-model group 567 M instead of 678 M.)
+// ---- kernel selection: the instance comes from mf_plan.h's row-width table ------------------------------------------------------------
 template <int ALGO, class T, int VEC, int LPR, int KI>
 void launch_batch_as(mi355rec_mf *h, const MfParams<T> &p, int grid, int batch_local, hipEvent_t e0, hipEvent_t e1) {
     // what the header's address is made of goes in front of the parameter block (see mf_batch_kernel); constants of the launch, and
@@ -171,8 +222,7 @@ void launch_batch_as(mi355rec_mf *h, const MfParams<T> &p, int grid, int batch_l
     const int4 *slot = p.slot_recs + (size_t)batch_local * p.slot_rec_stride;
     const int stamps = p.ticks != nullptr;
     auto go = [&](auto kernel) {
-        if (e0) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, e0, e1, 0, hdr, slot, p.tasks_per_batch, p.wg_base, p.wg_stride, stamps, p, batch_local);
-        else hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, h->stream, hdr, slot, p.tasks_per_batch, p.wg_base, p.wg_stride, stamps, p, batch_local);   // capturable
+        launch(kernel, dim3(grid), dim3(256), 0, h->stream, e0, e1, hdr, slot, p.tasks_per_batch, p.wg_base, p.wg_stride, stamps, p, batch_local);
     };
     if (p.sgd_mode == MI355REC_SGD) go(mf_batch_kernel<ALGO, T, VEC, LPR, KI, true>);
     else go(mf_batch_kernel<ALGO, T, VEC, LPR, KI, false>);
@@ -185,33 +235,10 @@ void launch_batch(mi355rec_mf *h, const MfParams<T> &p, int batch_local, bool ti
     if (grid == 0) return;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (timed) h->dispatch_timers.next(e0, e1, h->max_timed);
-    const int k = h->k, chunks = k / VEC;
-    if (k % VEC == 0 && chunks <= 16) launch_batch_as<ALGO, T, VEC, 16, 1>(h, p, grid, batch_local, e0, e1);
-    else if (k % VEC == 0 && chunks <= 32) launch_batch_as<ALGO, T, VEC, 32, 1>(h, p, grid, batch_local, e0, e1);
-    else if (k % VEC == 0 && chunks <= 64) launch_batch_as<ALGO, T, VEC, 64, 1>(h, p, grid, batch_local, e0, e1);
-    else if (k % VEC == 0 && chunks <= 128) launch_batch_as<ALGO, T, VEC, 64, 2>(h, p, grid, batch_local, e0, e1);
-    else if (e0) hipExtLaunchKernelGGL((mf_batch_generic_kernel<ALGO, T>), dim3(grid), dim3(256), 0, h->stream, e0, e1, 0, p, batch_local);
-    else hipLaunchKernelGGL((mf_batch_generic_kernel<ALGO, T>), dim3(grid), dim3(256), 0, h->stream, p, batch_local);
-}
-
-// instance of the mini-batch kernel a model runs on (must mirror launch_batch); -1: the any-k kernel
-int kernel_class(const mi355rec_mf *h) {
-    const int vec = h->f64 ? 2 : 4, k = h->k;
-    if (k % vec != 0) return -1;
-    const int chunks = k / vec;
-    return chunks <= 16 ? 0 : (chunks <= 32 ? 1 : (chunks <= 64 ? 2 : (chunks <= 128 ? 3 : -1)));
-}
-
-template <int ALGO, class T, int VEC, int LPR, int KI>
-void launch_group_as(hipStream_t s, const MfParams<T> *table, dim3 grid, int batch_local, bool plain_sgd, hipEvent_t e0, hipEvent_t e1) {
-    // (a 64-VGPR build for 8 wavefronts per SIMD was measured twice and is gone: 20 spilled registers, 422 M against 678 M samples/s)
-    if (plain_sgd) {
-        if (e0) hipExtLaunchKernelGGL((mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, true>), grid, dim3(256), 0, s, e0, e1, 0, table, batch_local);
-        else hipLaunchKernelGGL((mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, true>), grid, dim3(256), 0, s, table, batch_local);
-        return;
-    }
-    if (e0) hipExtLaunchKernelGGL((mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, false>), grid, dim3(256), 0, s, e0, e1, 0, table, batch_local);
-    else hipLaunchKernelGGL((mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, false>), grid, dim3(256), 0, s, table, batch_local);
+    const bool found = dispatch_width(row_width(h->k, sizeof(T) == 8).klass, [&](auto lpr, auto ki) {
+        launch_batch_as<ALGO, T, VEC, decltype(lpr)::value, decltype(ki)::value>(h, p, grid, batch_local, e0, e1);
+    });
+    if (!found) launch(mf_batch_generic_kernel<ALGO, T>, dim3(grid), dim3(256), 0, h->stream, e0, e1, p, batch_local);
 }
 
 template <int ALGO, class T>
@@ -219,12 +246,12 @@ void launch_group_batch(hipStream_t s, const MfParams<T> *table, int klass, int 
                         hipEvent_t e0, hipEvent_t e1) {
     constexpr int VEC = 16 / (int)sizeof(T);
     const dim3 grid(wgs, n_models);
-    switch (klass) {
-        case 0: launch_group_as<ALGO, T, VEC, 16, 1>(s, table, grid, batch_local, plain_sgd, e0, e1); break;
-        case 1: launch_group_as<ALGO, T, VEC, 32, 1>(s, table, grid, batch_local, plain_sgd, e0, e1); break;
-        case 2: launch_group_as<ALGO, T, VEC, 64, 1>(s, table, grid, batch_local, plain_sgd, e0, e1); break;
-        default: launch_group_as<ALGO, T, VEC, 64, 2>(s, table, grid, batch_local, plain_sgd, e0, e1); break;
-    }
+    // (a 64-VGPR build for 8 wavefronts per SIMD was measured twice and is gone: 20 spilled registers, 422 M against 678 M samples/s)
+    dispatch_width(klass, [&](auto lpr, auto ki) {
+        constexpr int LPR = decltype(lpr)::value, KI = decltype(ki)::value;
+        if (plain_sgd) launch(mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, true>, grid, dim3(256), 0, s, e0, e1, table, batch_local);
+        else launch(mf_group_batch_kernel<ALGO, T, VEC, LPR, KI, false>, grid, dim3(256), 0, s, e0, e1, table, batch_local);
+    });
 }
 
 template <class T>
@@ -236,74 +263,40 @@ void launch_sampler(mi355rec_mf *h, const MfParams<T> &p, hipStream_t on = nullp
     hipLaunchKernelGGL(mf_epoch_advance_kernel, dim3(1), dim3(64), 0, s, p.state);
 }
 
-int pow2_at_least(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// samples of a task's list a wavefront of the mini-batch kernel works on at a time (must mirror launch_batch)
-int samples_in_flight(const mi355rec_mf *h) {
-    const int vec = h->f64 ? 2 : 4, k = h->k;
-    if (k % vec != 0 || k / vec > 128) return 1;
-    const int chunks = k / vec;
-    return chunks <= 16 ? 4 : (chunks <= 32 ? 2 : 1);
-}
-
-bool fast_schedule_fits(const mi355rec_mf *h, long long n_batches) {
-    const int tpb = per_sample(h) * h->cfg.batch_size;
-    return !getenv("MI355REC_MF_GENERAL_SCHEDULE") && n_batches <= FAST_MAX_BATCHES && tpb <= FAST_MAX_SLOTS &&
-           bits_for((unsigned long long)h->n_users + h->n_items) + bits_for((unsigned long long)std::max(tpb, SCHED_THREADS)) <= 31 &&
-           (h->k % (h->f64 ? 2 : 4) == 0 && h->k / (h->f64 ? 2 : 4) <= 128);    // the any-k kernel does not split wide lists
-}
-
-// keys, run starts, header slots (words) + one byte per incidence for the once-touched flags
-size_t sched_mid_bytes(int np) {
-    const size_t middle = std::max(sizeof(unsigned) * (2 * (size_t)np + 1), sched_sort_storage_bytes(np));      // run starts + header slots | sort scratch
-    return (middle + 15) & ~(size_t)15;
-}
-size_t sched_lds_bytes(int np) { return sizeof(unsigned) * (size_t)np + sched_mid_bytes(np) + (size_t)np + 16; }
+// ---- schedules ------------------------------------------------------------------------------------------------------------------
+size_t sched_lds(int np) { return sched_lds_bytes(np, sched_sort_storage_bytes(np)); }
 
 void set_sched_sort_attribute(const void *kernel, bool (&attr_set)[64]) {
     int dev = 0;
     MI_HIP(hipGetDevice(&dev));                 // the attribute is per DEVICE, not per process
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        MI_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sched_lds_bytes(FAST_MAX_SLOTS)));
+        MI_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sched_lds(FAST_MAX_SLOTS)));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
 }
 
-FastSchedParams fast_sched_params(mi355rec_mf *h, long long n_samples) {
+FastSchedParams fast_sched_params(mi355rec_mf *h, const MfKnobs &knobs, long long n_samples) {
+    const MfShape s = shape_of(h);
+    const FastSchedNumbers n = fast_sched_numbers(s, knobs, sched_sort_storage_bytes(sched_np(tasks_per_batch(s))));
     FastSchedParams f;
     memset(&f, 0, sizeof(f));                   // (padding bytes included: the group compares tables bytewise)
     f.n_samples = n_samples;
-    f.per = per_sample(h);
+    f.per = per_sample(s);
     f.n_users = h->n_users;
     f.n_entries = h->n_users + h->n_items;
     f.batch_size = h->cfg.batch_size;
-    f.tasks_per_batch = f.per * h->cfg.batch_size;
-    f.np = std::max(SCHED_THREADS, pow2_at_least(f.tasks_per_batch));
-    f.slot_bits = bits_for((unsigned long long)f.np);
-    f.entry_bits = std::min(32 - f.slot_bits, bits_for((unsigned long long)f.n_entries) + 1);
-    f.mid_bytes = (int)sched_mid_bytes(f.np);
-    f.words = FAST_MAX_BATCHES / 32;
-    f.group = samples_in_flight(h);
-    f.su = h->su.ptr; f.si = h->si.ptr; f.sj = h->sj.ptr; f.sr = h->sr.ptr;
-    f.touched = h->touched.ptr; f.par = h->par.ptr;
-    f.sorted_slot = h->sorted_slot.ptr; f.qtask = h->qtask.ptr; f.used = h->used.ptr;
-    f.tasks = h->tasks.ptr; f.recs = h->recs.ptr; f.slot_recs = h->slot_recs.ptr;
-    // fused sample tasks: BPR only; not in the exact multi-GPU mode, whose exchange slabs hold one row per task slot
-    f.fuse = h->cfg.algorithm == MI355REC_MF_BPR && h->shard_rank < 0 && !getenv("MI355REC_MF_NO_FUSE");
-    f.fill_all = 1;
-    f.ticks = h->sched_ticks.ptr;
+    f.tasks_per_batch = tasks_per_batch(s);
+    f.np = n.np; f.slot_bits = n.slot_bits; f.entry_bits = n.entry_bits; f.mid_bytes = n.mid_bytes;
+    f.words = n.words; f.group = n.group; f.fuse = n.fuse; f.fill_all = n.fill_all;
+    f.su = h->buf.su.ptr; f.si = h->buf.si.ptr; f.sj = h->buf.sj.ptr; f.sr = h->buf.sr.ptr;
+    f.touched = h->lds.touched.ptr; f.par = h->par.ptr;
+    f.sorted_slot = h->lds.sorted_slot.ptr; f.qtask = h->lds.qtask.ptr; f.used = h->lds.used.ptr;
+    f.tasks = h->buf.tasks.ptr; f.recs = h->buf.recs.ptr; f.slot_recs = h->buf.slot_recs.ptr;
+    f.ticks = h->lds.ticks.ptr;
     return f;
 }
 
-// A native epoch whose whole stream goes through ONE in-LDS schedule is drawn by that schedule's workgroups (FastSchedParams::draw):
-// no sampler launch, no epoch-advance launch, no read-back of the stream.  Everything else keeps launch_sampler: replayed streams,
-// streams scheduled FAST_MAX_BATCHES mini-batches at a time, the radix-sort schedule, the group, the exact multi-GPU mode, AsySVD.
-bool schedule_draws(const mi355rec_mf *h);
-
+// the schedule's workgroups draw the epoch's samples themselves (schedule_draws)
 template <class T>
 void set_draw(FastSchedParams &f, const MfParams<T> &p) {
     f.draw = 1;
@@ -319,112 +312,95 @@ void set_draw(FastSchedParams &f, const MfParams<T> &p) {
     f.indptr = p.indptr; f.indices = p.indices; f.data = p.data;
 }
 
-void enqueue_fast_schedule(mi355rec_mf *h, long long n_samples, long long n_batches, const FastSchedParams *given = nullptr,
-                           hipStream_t on = nullptr) {
-    hipStream_t s = on ? on : h->stream;
-    const FastSchedParams f = given ? *given : fast_sched_params(h, n_samples);
-    const size_t lds = sched_lds_bytes(f.np);
+void enqueue_fast_schedule(mi355rec_mf *h, const FastSchedParams &f, long long n_batches) {
+    hipStream_t s = h->stream;
     static bool attr_set[64] = {};
     set_sched_sort_attribute(reinterpret_cast<const void *>(mf_sched_sort_kernel), attr_set);
-    hipLaunchKernelGGL(mf_sched_sort_kernel, dim3((unsigned)n_batches), dim3(SCHED_THREADS), lds, s, f);
+    hipLaunchKernelGGL(mf_sched_sort_kernel, dim3((unsigned)n_batches), dim3(SCHED_THREADS), sched_lds(f.np), s, f);
     hipLaunchKernelGGL(mf_sched_emit_kernel, dim3(div_up(f.batch_size, 256), (unsigned)n_batches), dim3(256), 0, s, f);
     hipLaunchKernelGGL(mf_sched_finish_kernel, dim3(div_up(f.n_entries, 256)), dim3(256), 0, s, f);
 }
 
+SchedParams radix_sched_params(mi355rec_mf *h, const GeneralSched &g, long long n_samples) {
+    const MfShape s = shape_of(h);
+    const long long n = n_samples * per_sample(s);
+    auto &r = h->radix;
+    SchedParams sp{};
+    sp.n_samples = n_samples;
+    sp.per = per_sample(s);
+    sp.n_users = h->n_users;
+    sp.batch_size = h->cfg.batch_size;
+    sp.batch_bits = g.batch_bits;
+    sp.tasks_per_batch = tasks_per_batch(s);
+    sp.su = h->buf.su.ptr; sp.si = h->buf.si.ptr; sp.sj = h->buf.sj.ptr; sp.sr = h->buf.sr.ptr;
+    sp.keys = r.keys.ptr; sp.slots = r.slots.ptr;
+    sp.keys_sorted = r.keys_sorted.ptr; sp.slots_sorted = r.slots_sorted.ptr;
+    sp.head = r.head.ptr; sp.head_scan = r.head_scan.ptr; sp.task_at = r.task_at.ptr;
+    sp.spar = r.spar.ptr; sp.par = h->par.ptr;
+    sp.batch_count = g.by_rank ? nullptr : r.batch_count.ptr;
+    // (the unsorted keys are dead after the sort: their buffer holds the first-incidence flags and their scan, n ints each)
+    sp.slot_flag = reinterpret_cast<int *>(r.keys.ptr);
+    sp.slot_rank = reinterpret_cast<int *>(r.keys.ptr) + n;
+    sp.tasks = h->buf.tasks.ptr; sp.recs = h->buf.recs.ptr;
+    return sp;
+}
+
 // Stream buffers -> tasks (all on the handle's stream, no host synchronisation: capturable).
-void enqueue_schedule(mi355rec_mf *h, long long n_samples, long long n_batches) {
-    if (h->fast_schedule && fast_schedule_fits(h, n_batches)) {
-        enqueue_fast_schedule(h, n_samples, n_batches);
+void enqueue_schedule(mi355rec_mf *h, const MfKnobs &knobs, long long n_samples, long long n_batches) {
+    const MfShape shape = shape_of(h);
+    if (runs_fast_schedule(shape, knobs, n_batches)) {
+        enqueue_fast_schedule(h, fast_sched_params(h, knobs, n_samples), n_batches);
         return;
     }
     hipStream_t s = h->stream;
-    const int per = per_sample(h);
-    const long long n = n_samples * per;
-    SchedParams sp{};
-    sp.n_samples = n_samples;
-    sp.per = per;
-    sp.n_users = h->n_users;
-    sp.batch_size = h->cfg.batch_size;
-    sp.batch_bits = bits_for((unsigned long long)n_batches);
-    sp.tasks_per_batch = per * h->cfg.batch_size;
-    sp.su = h->su.ptr; sp.si = h->si.ptr; sp.sj = h->sj.ptr; sp.sr = h->sr.ptr;
-    sp.keys = h->keys.ptr; sp.slots = h->slots.ptr;
-    sp.keys_sorted = h->keys_sorted.ptr; sp.slots_sorted = h->slots_sorted.ptr;
-    sp.head = h->head.ptr; sp.head_scan = h->head_scan.ptr; sp.task_at = h->task_at.ptr;
-    sp.spar = h->spar.ptr; sp.par = h->par.ptr; // placement of the headers inside a batch: by rank (reproducible layout) for the exact multi-GPU mode and for batches too large
-    // for the in-LDS schedule; by counter for streams of many small batches (see mf_tasks_kernel)
-    const bool by_rank = h->shard_rank >= 0 || sp.tasks_per_batch > FAST_MAX_SLOTS;
-    sp.batch_count = by_rank ? nullptr : h->batch_count.ptr;
-    // (the unsorted keys are dead after the sort: their buffer holds the first-incidence flags and their scan, n ints each)
-    sp.slot_flag = reinterpret_cast<int *>(h->keys.ptr);
-    sp.slot_rank = reinterpret_cast<int *>(h->keys.ptr) + n;
-    sp.tasks = h->tasks.ptr; sp.recs = h->recs.ptr;
-    const int end_bit = sp.batch_bits + bits_for((unsigned long long)h->n_users + h->n_items);
-    MI_REQUIRE(end_bit <= 64, "sample stream too long for the schedule keys");
-    MI_HIP(hipMemsetAsync(h->batch_count.ptr, 0, sizeof(int) * (size_t)n_batches, s));
-    MI_HIP(hipMemsetAsync(h->tasks.ptr, 0, sizeof(TaskHeader) * (size_t)n_batches * sp.tasks_per_batch, s));
+    auto &r = h->radix;
+    const GeneralSched g = general_sched(shape, n_batches);
+    const SchedParams sp = radix_sched_params(h, g, n_samples);
+    const long long n = n_samples * sp.per;
+    MI_REQUIRE(g.fits, "sample stream too long for the schedule keys");
+    MI_HIP(hipMemsetAsync(r.batch_count.ptr, 0, sizeof(int) * (size_t)n_batches, s));
+    MI_HIP(hipMemsetAsync(h->buf.tasks.ptr, 0, sizeof(TaskHeader) * (size_t)n_batches * sp.tasks_per_batch, s));
     hipLaunchKernelGGL(mf_keys_kernel, dim3(div_up(n_samples, 256)), dim3(256), 0, s, sp);
-    size_t bytes = h->cub_tmp_bytes;
-    MI_HIP(rocprim::radix_sort_pairs(h->cub_tmp.ptr, bytes, h->keys.ptr, h->keys_sorted.ptr, h->slots.ptr,
-                                              h->slots_sorted.ptr, (int)n, 0, end_bit, s));
+    size_t bytes = r.cub_tmp_bytes;
+    MI_HIP(rocprim::radix_sort_pairs(r.cub_tmp.ptr, bytes, r.keys.ptr, r.keys_sorted.ptr, r.slots.ptr, r.slots_sorted.ptr, (int)n, 0, g.end_bit, s));
     MI_HIP(hipMemsetAsync(sp.slot_flag, 0, sizeof(int) * (size_t)n, s));
     hipLaunchKernelGGL(mf_heads_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, sp);
-    bytes = h->cub_tmp_bytes;
-    MI_HIP(rocprim::inclusive_scan(h->cub_tmp.ptr, bytes, h->head.ptr, h->head_scan.ptr, (size_t)n, rocprim::plus<int>(), s));
-    bytes = h->cub_tmp_bytes;
-    MI_HIP(rocprim::exclusive_scan(h->cub_tmp.ptr, bytes, sp.slot_flag, reinterpret_cast<int *>(h->keys.ptr) + n, 0, (size_t)n, rocprim::plus<int>(), s));
+    bytes = r.cub_tmp_bytes;
+    MI_HIP(rocprim::inclusive_scan(r.cub_tmp.ptr, bytes, r.head.ptr, r.head_scan.ptr, (size_t)n, rocprim::plus<int>(), s));
+    bytes = r.cub_tmp_bytes;
+    MI_HIP(rocprim::exclusive_scan(r.cub_tmp.ptr, bytes, sp.slot_flag, reinterpret_cast<int *>(r.keys.ptr) + n, 0, (size_t)n, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(mf_tasks_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, sp);
     hipLaunchKernelGGL(mf_recs_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, sp);
 }
 
-// Mini-batches per schedule.  A stream the in-LDS schedule cannot hold at once (more than FAST_MAX_BATCHES mini-batches: FunkSVD's
-// epoch at the ML-20M shape has 20 001) is scheduled and run FAST_MAX_BATCHES mini-batches at a time, each part a stream of its
-// own (its end moves the global batch index and the global-bias ring on): three schedule launches per 256 mini-batch launches,
-// against the radix-sort schedule of the whole stream they keep the split of long lists over a workgroup (a list of 10
-// held the kernel for 14 000 cycles where the median wavefront took 7 300), headers and records in 16 MB that stay cached instead of
-// 1.9 GB, and 1.5 GB of sort buffers are never allocated.  Whole stream: when it fits, when the in-LDS schedule is not available
-// for this handle, and in the exact multi-GPU mode (its exchange walks one schedule).
-long long schedule_span(const mi355rec_mf *h, long long n_batches) {
-    if (h->shard_rank < 0 && n_batches > FAST_MAX_BATCHES && fast_schedule_fits(h, 1) && !getenv("MI355REC_MF_WHOLE_STREAM_SCHEDULE"))
-        return FAST_MAX_BATCHES;
-    return n_batches;
-}
-
-bool schedule_draws(const mi355rec_mf *h) {
-    const long long nb = batches_per_epoch(h);
-    return h->cfg.algorithm != MI355REC_MF_ASY_SVD && h->shard_rank < 0 && h->fast_schedule && fast_schedule_fits(h, nb) &&
-           schedule_span(h, nb) == nb;
+// the schedule a step of the stream walk asks for (StreamStep::sched)
+template <class T>
+void enqueue_step_schedule(mi355rec_mf *h, const MfKnobs &knobs, const MfParams<T> &p, const StreamStep &st) {
+    if (st.sched == SCHED_WHOLE) {
+        enqueue_schedule(h, knobs, st.sched_samples, st.sched_batches);
+        return;
+    }
+    FastSchedParams f = fast_sched_params(h, knobs, st.sched_samples);
+    if (st.sched == SCHED_DRAW) set_draw(f, p);
+    f.su += st.sample_offset; f.si += st.sample_offset; f.sj += st.sample_offset; f.sr += st.sample_offset;     // (a part: a stream of its own)
+    enqueue_fast_schedule(h, f, st.sched_batches);
 }
 
 // mini-batches first .. last - 1 of a stream of n_batches, with the schedules and stream ends that fall into that range
 template <class T>
-void enqueue_stream(mi355rec_mf *h, const MfParams<T> &p, long long n_samples, long long n_batches, bool timed, long long first = 0,
-                    long long last = -1, bool draw = false) {
+void enqueue_stream(mi355rec_mf *h, const MfKnobs &knobs, const MfParams<T> &p, long long n_samples, long long n_batches, bool timed,
+                    long long first = 0, long long last = -1, bool draw = false) {
     const bool bpr = h->cfg.algorithm == MI355REC_MF_BPR;
-    const long long span = schedule_span(h, n_batches), B = h->cfg.batch_size;
+    const long long span = schedule_span(shape_of(h), knobs, n_batches), B = h->cfg.batch_size;
     if (last < 0) last = n_batches;
     for (long long b = first; b < last; ++b) {
-        const long long part = b / span * span, local = b - part, part_batches = std::min(span, n_batches - part);
-        if (local == 0) {
-            if (draw) {                 // (schedule_draws: one span on the in-LDS schedule)
-                FastSchedParams f = fast_sched_params(h, n_samples);
-                set_draw(f, p);
-                enqueue_fast_schedule(h, n_samples, n_batches, &f);
-            } else if (span == n_batches) {
-                enqueue_schedule(h, n_samples, n_batches);
-            } else {
-                FastSchedParams f = fast_sched_params(h, std::min(n_samples - part * B, part_batches * B));
-                f.su += part * B; f.si += part * B; f.sj += part * B; f.sr += part * B;
-                enqueue_fast_schedule(h, f.n_samples, part_batches, &f);
-            }
-        }
-        if (bpr) launch_batch<MI355REC_MF_BPR, T>(h, p, (int)local, timed);
-        else launch_batch<MI355REC_MF_FUNK_SVD, T>(h, p, (int)local, timed);
-        if (local + 1 == part_batches) hipLaunchKernelGGL(mf_stream_end_kernel<T>, dim3(1), dim3(64), 0, h->stream, p, part_batches);
+        const StreamStep st = stream_step(n_samples, n_batches, span, B, draw, b);
+        if (st.sched != SCHED_NONE) enqueue_step_schedule(h, knobs, p, st);
+        if (bpr) launch_batch<MI355REC_MF_BPR, T>(h, p, st.local, timed);
+        else launch_batch<MI355REC_MF_FUNK_SVD, T>(h, p, st.local, timed);
+        if (st.end_batches) hipLaunchKernelGGL(mf_stream_end_kernel<T>, dim3(1), dim3(64), 0, h->stream, p, st.end_batches);
     }
 }
-
-constexpr int ASY_CHUNK = 1 << 16;   // steps per launch of the ordered AsySVD kernel (keeps single launches short)
 
 template <class T>
 void enqueue_asy_steps(mi355rec_mf *h, const MfParams<T> &p, long long n_steps, bool timed) {
@@ -432,10 +408,7 @@ void enqueue_asy_steps(mi355rec_mf *h, const MfParams<T> &p, long long n_steps, 
         const int count = (int)std::min<long long>(ASY_CHUNK, n_steps - first);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) h->dispatch_timers.next(e0, e1, h->max_timed);
-        auto go = [&](auto kernel) {
-            if (e0) hipExtLaunchKernelGGL(kernel, dim3(1), dim3(1024), 0, h->stream, e0, e1, 0, p, first, count);
-            else hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), 0, h->stream, p, first, count);
-        };
+        auto go = [&](auto kernel) { launch(kernel, dim3(1), dim3(1024), 0, h->stream, e0, e1, p, first, count); };
         if (h->k <= 64) go(mf_asy_kernel<T, 1>);
         else if (h->k <= 128) go(mf_asy_kernel<T, 2>);
         else go(mf_asy_kernel<T, 4>);
@@ -445,127 +418,106 @@ void enqueue_asy_steps(mi355rec_mf *h, const MfParams<T> &p, long long n_steps, 
 // One native epoch as plain launches (the first `max_timed` mini-batch launches carry per-dispatch events when `timed`) -- or the
 // part of it that holds mini-batches first .. last - 1: sampler and schedule go with the first part.
 template <class T>
-void enqueue_epoch(mi355rec_mf *h, const MfParams<T> &p, bool timed, long long first = 0, long long last = -1) {
-    const bool draw = schedule_draws(h);
+void enqueue_epoch(mi355rec_mf *h, const MfKnobs &knobs, const MfParams<T> &p, bool timed, long long first = 0, long long last = -1) {
+    const MfShape s = shape_of(h);
+    const bool draw = schedule_draws(s, knobs);
     if (first == 0 && !draw) launch_sampler(h, p);
     if (h->cfg.algorithm == MI355REC_MF_ASY_SVD) {
         enqueue_asy_steps(h, p, p.samples_per_epoch, timed);
         return;
     }
-    enqueue_stream(h, p, p.samples_per_epoch, batches_per_epoch(h), timed, first, last, draw);
+    enqueue_stream(h, knobs, p, p.samples_per_epoch, batches_per_epoch(s), timed, first, last, draw);
 }
 
 // Capture one epoch into graphs of up to GRAPH_SEGMENT mini-batches (once per handle; re-captured only if the stream buffers are
-// re-allocated).  FunkSVD's epoch at the ML-20M shape is 20 001 mini-batches: as plain launches the host's launch rate (8.8 us
-// per mini-batch) was the bound, not the chain of kernels.
-constexpr long long GRAPH_SEGMENT = 4096, MAX_GRAPH_BATCHES = 64 * GRAPH_SEGMENT;
+// re-allocated).
 template <class T>
-void ensure_epoch_graph(mi355rec_mf *h, const MfParams<T> &p) {
-    if (!h->epoch_graphs.empty() || h->graph_failed) return;
-    const long long nb = h->cfg.algorithm == MI355REC_MF_ASY_SVD ? 1 : batches_per_epoch(h);
-    for (long long first = 0; first < nb; first += GRAPH_SEGMENT) {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t exec = nullptr;
-        hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            try {
-                enqueue_epoch(h, p, false, first, std::min(nb, first + GRAPH_SEGMENT));
-            } catch (...) {
-                (void)hipStreamEndCapture(h->stream, &g);
-                if (g) (void)hipGraphDestroy(g);
-                (void)hipGetLastError();
-                h->drop_graphs();
-                h->graph_failed = true;
-                return;
-            }
-            e = hipStreamEndCapture(h->stream, &g);
-        }
-        if (e == hipSuccess) e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (e != hipSuccess) {       // plain launches remain correct, only slower: remember and go on
-            (void)hipGetLastError();
+void ensure_epoch_graph(mi355rec_mf *h, const MfKnobs &knobs, const MfParams<T> &p) {
+    if (!h->graphs.epoch.empty() || h->graphs.failed) return;
+    const long long nb = graph_batches(shape_of(h));
+    for (long long i = 0; i < graph_segments(nb); ++i) {
+        const BatchRange r = graph_segment(nb, i);
+        hipGraphExec_t exec = capture_graph(h->stream, [&] { enqueue_epoch(h, knobs, p, false, r.first, r.last); });
+        if (!exec) {                 // remember and go on with plain launches
             h->drop_graphs();
-            h->graph_failed = true;
+            h->graphs.failed = true;
             return;
         }
-        h->epoch_graphs.push_back(exec);
+        h->graphs.epoch.push_back(exec);
     }
+}
+
+// ---- buffers (what and how much: BufferPlan) ------------------------------------------------------------------------------------------
+void alloc_radix_buffers(mi355rec_mf *h, const BufferPlan &b, size_t n_samples) {
+    h->drop_graphs();
+    const size_t n = b.incidences;
+    MI_REQUIRE(b.incidences_fit, "sample stream too long (%zu incidences)", n);
+    auto &r = h->radix;
+    r.keys.alloc(n); r.keys_sorted.alloc(n);
+    r.slots.alloc(n); r.slots_sorted.alloc(n);
+    r.head.alloc(n); r.head_scan.alloc(n); r.task_at.alloc(n);
+    r.spar.alloc(n);
+    size_t sort_bytes = 0, scan_bytes = 0;
+    MI_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, r.keys.ptr, r.keys_sorted.ptr, r.slots.ptr, r.slots_sorted.ptr, (int)n, 0, 64, h->stream));
+    MI_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, r.head.ptr, r.head_scan.ptr, (size_t)n, rocprim::plus<int>(), h->stream));
+    r.cub_tmp_bytes = std::max(sort_bytes, scan_bytes) + 256;
+    r.cub_tmp.alloc(r.cub_tmp_bytes);
+    r.capacity = n_samples;
+}
+
+void alloc_task_tables(mi355rec_mf *h, const BufferPlan &b) {
+    h->drop_graphs();
+    h->radix.batch_count.alloc(b.batch_count);
+    h->buf.tasks.alloc(b.tasks);
+    MI_HIP(hipMemsetAsync(h->buf.tasks.ptr, 0, sizeof(TaskHeader) * b.tasks, h->stream));
+    h->buf.recs.alloc(b.recs);
+    h->lds.fast_schedule = b.fast1;
+    h->buf.slot_recs.alloc_zero(b.slot_recs, h->stream);
+    if (b.fast1) {
+        h->lds.sorted_slot.alloc(b.sorted_slot);
+        h->lds.qtask.alloc(b.qtask);
+        h->lds.used.alloc(b.used);
+        if (!h->lds.touched.ptr) h->lds.touched.alloc_zero(b.touched, h->stream);
+    }
+    h->buf.batch_capacity = b.table_batches;
 }
 
 // `whole_stream`: the caller schedules the stream in one piece whatever its length (group members, exact multi-GPU mode)
-void ensure_stream_capacity(mi355rec_mf *h, size_t n_samples, long long n_batches, bool whole_stream = false) {
-    const bool asy = h->cfg.algorithm == MI355REC_MF_ASY_SVD;
-    if (h->stream_capacity < n_samples) {
+void ensure_stream_capacity(mi355rec_mf *h, const MfKnobs &knobs, size_t n_samples, long long n_batches, bool whole_stream = false) {
+    const BufferPlan b = buffer_plan(shape_of(h), knobs, n_samples, n_batches, whole_stream);
+    if (h->buf.capacity < n_samples) {
         h->drop_graphs();       // they hold the old buffer addresses
-        h->su.alloc(n_samples);
-        h->si.alloc(n_samples);
-        h->sj.alloc(n_samples);
-        h->sr.alloc(n_samples);
-        h->stream_capacity = n_samples;
+        h->buf.su.alloc(n_samples);
+        h->buf.si.alloc(n_samples);
+        h->buf.sj.alloc(n_samples);
+        h->buf.sr.alloc(n_samples);
+        h->buf.capacity = n_samples;
     }
-    if (asy) return;
-    const bool fast1 = fast_schedule_fits(h, 1);
-    // the radix-sort schedule's buffers: only for streams it will actually see
-    whole_stream = whole_stream || getenv("MI355REC_MF_WHOLE_STREAM_SCHEDULE");
-    const bool general = !fast1 || (whole_stream && !fast_schedule_fits(h, n_batches));
-    if (general && h->general_capacity < n_samples) {
-        h->drop_graphs();
-        const size_t n = n_samples * (size_t)per_sample(h);
-        MI_REQUIRE(n < (1ull << 31), "sample stream too long (%zu incidences)", n);
-        h->keys.alloc(n); h->keys_sorted.alloc(n);
-        h->slots.alloc(n); h->slots_sorted.alloc(n);
-        h->head.alloc(n); h->head_scan.alloc(n); h->task_at.alloc(n);
-        h->spar.alloc(n);
-        size_t sort_bytes = 0, scan_bytes = 0;
-        MI_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, h->keys.ptr, h->keys_sorted.ptr, h->slots.ptr,
-                                                  h->slots_sorted.ptr, (int)n, 0, 64, h->stream));
-        MI_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, h->head.ptr, h->head_scan.ptr, (size_t)n, rocprim::plus<int>(), h->stream));
-        h->cub_tmp_bytes = std::max(sort_bytes, scan_bytes) + 256;
-        h->cub_tmp.alloc(h->cub_tmp_bytes);
-        h->general_capacity = n_samples;
-    }
-    // headers and records: per mini-batch of a SCHEDULE (a long stream on the in-LDS schedule reuses FAST_MAX_BATCHES of them)
-    const long long table_batches = general ? n_batches : std::min<long long>(n_batches, FAST_MAX_BATCHES);
-    if (h->batch_capacity < table_batches) {
-        h->drop_graphs();
-        const size_t tpb = (size_t)per_sample(h) * h->cfg.batch_size;
-        h->batch_count.alloc((size_t)table_batches);
-        h->tasks.alloc((size_t)(table_batches + 1) * tpb);
-        MI_HIP(hipMemsetAsync(h->tasks.ptr, 0, sizeof(TaskHeader) * (size_t)(table_batches + 1) * tpb, h->stream));
-        h->recs.alloc((size_t)table_batches * tpb);          // records of batch b start at b * tpb in both schedule paths
-        h->fast_schedule = fast1;
-        // (the mini-batch kernel reads a slot's pair records whatever the schedule: without the in-LDS schedule one mini-batch of zeros)
-        h->slot_recs.alloc_zero(3 * tpb * (size_t)(fast1 ? table_batches : 1), h->stream);
-        if (h->fast_schedule) {
-            h->sorted_slot.alloc((size_t)table_batches * tpb);
-            h->qtask.alloc((size_t)table_batches * tpb);
-            h->used.alloc((size_t)table_batches);
-            if (!h->touched.ptr) h->touched.alloc_zero(((size_t)h->n_users + h->n_items) * (FAST_MAX_BATCHES / 32), h->stream);
-        }
-        h->batch_capacity = table_batches;
-    }
+    if (b.asy) return;
+    if (b.general && h->radix.capacity < n_samples) alloc_radix_buffers(h, b, n_samples);   // only for streams that schedule will actually see
+    if (h->buf.batch_capacity < b.table_batches) alloc_task_tables(h, b);
 }
 
-double bytes_per_sample(const mi355rec_mf *h) {
-    // ALGORITHMIC lower bound of DESIGN.md section 4: every row a sample touches is read once and written once
-    // (3 rows for BPR, 2 for FunkSVD), fp32.
-    const double rows = h->cfg.algorithm == MI355REC_MF_BPR ? 3.0 : 2.0;   // (AsySVD: its profile-sized term is added per call)
-    return rows * 2.0 * 4.0 * (double)h->k;
-}
-
+// ---- calls ----------------------------------------------------------------------------------------------------------------------
 void begin_call(mi355rec_mf *h) {
     MI_HIP(hipMemsetAsync(h->loss_slots.ptr, 0, sizeof(double) * h->loss_slots.count, h->stream));
     MI_HIP(hipMemsetAsync(&h->state.ptr->asy_loss, 0, sizeof(double), h->stream));
     h->dispatch_timers.reset();
 }
 
-void finish_call(mi355rec_mf *h, long long n_samples, long long n_launches) {
-    MI_HIP(hipGetLastError());
+// the sum of the loss slots, once everything on the handle's stream is done
+double read_loss(mi355rec_mf *h) {
     h->host_loss.resize(h->loss_slots.count);
     h->loss_slots.download(h->host_loss.data(), h->loss_slots.count, h->stream);
     MI_HIP(hipStreamSynchronize(h->stream));
     double loss = 0;
     for (double v : h->host_loss) loss += v;
+    return loss;
+}
+
+void finish_call(mi355rec_mf *h, long long n_samples, long long n_launches) {
+    MI_HIP(hipGetLastError());
+    double loss = read_loss(h);
     if (h->cfg.algorithm == MI355REC_MF_ASY_SVD) {
         MfState st{};
         MI_HIP(hipMemcpy(&st, h->state.ptr, sizeof(MfState), hipMemcpyDeviceToHost));
@@ -576,7 +528,7 @@ void finish_call(mi355rec_mf *h, long long n_samples, long long n_launches) {
     h->stats.n_timed = h->dispatch_timers.used;
     h->stats.n_launches = n_launches;           // launches of the dominant (mini-batch) kernel
     h->stats.n_units = n_samples;
-    h->stats.algorithmic_bytes = bytes_per_sample(h) * (double)n_samples;
+    h->stats.algorithmic_bytes = bytes_per_sample(shape_of(h)) * (double)n_samples;
     h->stats.algorithmic_flops = 0;
     h->stats.loss = loss;
 }
@@ -610,53 +562,80 @@ void create_typed(mi355rec_mf *h, const void *U0, const void *V0) {
     h->asy_c_mu.alloc_zero(2 * ts, s);
 }
 
+void check_config(const mi355rec_mf_config *cfg, int32_t n_users, int32_t n_items) {
+    MI_REQUIRE(n_users > 0 && n_items > 0, "empty URM");
+    MI_REQUIRE(cfg->algorithm >= MI355REC_MF_BPR && cfg->algorithm <= MI355REC_MF_ASY_SVD,
+               "Value for 'algorithm_name' not recognized (%d)", cfg->algorithm);
+    const bool asy = cfg->algorithm == MI355REC_MF_ASY_SVD;
+    MI_REQUIRE(!asy || cfg->batch_size == 1, "Batch size other than 1 not supported for ASY_SVD");
+    if (asy && cfg->n_factors > ASY_KMAX)
+        fail(MI355REC_E_UNSUPPORTED, "ASY_SVD: n_factors = %d exceeds %d", cfg->n_factors, ASY_KMAX);
+    MI_REQUIRE(cfg->sgd_mode >= MI355REC_SGD && cfg->sgd_mode <= MI355REC_ADAM, "Value for 'sgd_mode' not recognized (%d)",
+               cfg->sgd_mode);
+    MI_REQUIRE(cfg->n_factors >= 1, "n_factors must be >= 1");
+    if (cfg->n_factors > 512) fail(MI355REC_E_UNSUPPORTED, "n_factors = %d exceeds 512", cfg->n_factors);
+    MI_REQUIRE(cfg->batch_size >= 1, "batch_size must be >= 1");
+    MI_REQUIRE(cfg->precision == MI355REC_F32 || cfg->precision == MI355REC_F64, "precision must be MI355REC_F32 or MI355REC_F64");
+}
+
+// what create allocates beside the factors: parities, tick buffers (MI355REC_MF_TICKS as this call sees it), loss slots, device state
+void create_state(mi355rec_mf *h, const MfKnobs &knobs) {
+    hipStream_t s = h->stream;
+    const MfShape shape = shape_of(h);
+    h->par.alloc_zero((size_t)h->n_users + h->n_items, s);
+    if (knobs.ticks) {
+        h->ticks.alloc_zero(tick_count(shape), s);
+        h->lds.ticks.alloc_zero(sched_tick_count(), s);
+    }
+    h->loss_slots.alloc_zero(loss_slot_count(shape), s);
+    h->state.alloc_zero(1, s);
+    MfState init{};     // Adam's running beta powers start at beta^1 (.pyx:217-218)
+    init.beta_1_power = h->cfg.beta_1;
+    init.beta_2_power = h->cfg.beta_2;
+    MI_HIP(hipMemcpyAsync(h->state.ptr, &init, sizeof(MfState), hipMemcpyHostToDevice, s));
+    MI_HIP(hipStreamSynchronize(s));
+}
+
 template <class T>
-void run_epochs_typed(mi355rec_mf *h, int n_epochs) {
+void run_epochs_typed(mi355rec_mf *h, const MfKnobs &knobs, int n_epochs) {
     const long long B = h->cfg.batch_size;
-    const long long per_epoch = batches_per_epoch(h);
-    const bool asy = h->cfg.algorithm == MI355REC_MF_ASY_SVD;
-    ensure_stream_capacity(h, (size_t)(per_epoch * B), per_epoch);
+    const long long per_epoch = batches_per_epoch(shape_of(h));
+    ensure_stream_capacity(h, knobs, (size_t)(per_epoch * B), per_epoch);
+    const MfShape s = shape_of(h);
     MfParams<T> p{};
     fill_params(h, p);
     begin_call(h);
-    // epochs whose mini-batch launches carry timing events run as plain launches, the rest replays the graph
-    const long long timed_epochs = h->max_timed > 0 ? std::min<long long>(n_epochs, (h->max_timed + per_epoch - 1) / per_epoch) : 0;
-    // MI355REC_NO_GRAPH=1: plain launches only (rocprofv3 on ROCm 7.2 crashes while tracing graph replays)
-    bool use_graph = per_epoch <= MAX_GRAPH_BATCHES && n_epochs - timed_epochs > 0 && !getenv("MI355REC_NO_GRAPH") && !asy;
-    if (use_graph) {
-        ensure_epoch_graph(h, p);
-        use_graph = !h->epoch_graphs.empty();
+    const long long timed = timed_epochs(h->max_timed, per_epoch, n_epochs);
+    bool graph = use_graph(s, knobs, per_epoch, n_epochs, timed);
+    if (graph) {
+        ensure_epoch_graph(h, knobs, p);
+        graph = !h->graphs.epoch.empty();
     }
     h->timer.start(h->stream);
     for (long long e = 0; e < n_epochs; ++e) {
-        if (e < timed_epochs || !use_graph) enqueue_epoch(h, p, e < timed_epochs);
-        else for (hipGraphExec_t g : h->epoch_graphs) MI_HIP(hipGraphLaunch(g, h->stream));
+        if (e < timed || !graph) enqueue_epoch(h, knobs, p, e < timed);
+        else for (hipGraphExec_t g : h->graphs.epoch) MI_HIP(hipGraphLaunch(g, h->stream));
     }
     h->timer.stop(h->stream);
     h->batches_done += per_epoch * n_epochs;
     h->last_call_samples = n_epochs > 0 ? per_epoch * B : 0;
-    finish_call(h, per_epoch * n_epochs * B, asy ? n_epochs * ((per_epoch + ASY_CHUNK - 1) / ASY_CHUNK) : per_epoch * n_epochs);
+    finish_call(h, per_epoch * n_epochs * B, n_launches(s, per_epoch, n_epochs));
 }
 
 template <class T>
-void run_samples_typed(mi355rec_mf *h, int64_t n) {
-    const long long B = h->cfg.batch_size;
+void run_samples_typed(mi355rec_mf *h, const MfKnobs &knobs, int64_t n) {
+    const MfShape s = shape_of(h);
+    const bool asy = h->cfg.algorithm == MI355REC_MF_ASY_SVD;
     MfParams<T> p{};
     fill_params(h, p);
-    const long long n_batches = (n + B - 1) / B;
+    const long long n_batches = asy ? n : ceil_div(n, h->cfg.batch_size);      // (AsySVD: single-sample steps)
     begin_call(h);
     h->timer.start(h->stream);
-    if (h->cfg.algorithm == MI355REC_MF_ASY_SVD) {
-        enqueue_asy_steps(h, p, n, true);
-        h->timer.stop(h->stream);
-        h->batches_done += n;
-        finish_call(h, n, (n + ASY_CHUNK - 1) / ASY_CHUNK);
-        return;
-    }
-    enqueue_stream(h, p, n, n_batches, true);
+    if (asy) enqueue_asy_steps(h, p, n, true);
+    else enqueue_stream(h, knobs, p, n, n_batches, true);
     h->timer.stop(h->stream);
     h->batches_done += n_batches;
-    finish_call(h, n, n_batches);
+    finish_call(h, n, n_launches(s, n_batches, 1));
 }
 
 // O = float (the float32 matrices north_star speaks of) or double (what the reference's getters return, .pyx:685-702: exact when
@@ -683,17 +662,16 @@ void get_factors_typed(mi355rec_mf *h, O *U, O *V, O *bu, O *bi, O *mu) {
     if (V) gather(p.V0, p.V1, par_v, h->n_items, h->k, V);
     if (bu) gather(p.bu0, p.bu1, par_u, h->n_users, 1, bu);
     if (bi) gather(p.bi0, p.bi1, par_v, h->n_items, 1, bi);
-    if (mu) {
-        if (asy) {
-            T v;
-            MI_HIP(hipMemcpyAsync(&v, p.asy_mu, sizeof(T), hipMemcpyDeviceToHost, s));
-            MI_HIP(hipStreamSynchronize(s));
-            *mu = (O)v;
-        } else {
-            hipLaunchKernelGGL((mf_final_mu_kernel<T, O>), dim3(1), dim3(64), 0, s, p, stage);
-            MI_HIP(hipMemcpyAsync(mu, stage, sizeof(O), hipMemcpyDeviceToHost, s));
-            MI_HIP(hipStreamSynchronize(s));
-        }
+    if (!mu) return;
+    if (asy) {
+        T v;
+        MI_HIP(hipMemcpyAsync(&v, p.asy_mu, sizeof(T), hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+        *mu = (O)v;
+    } else {
+        hipLaunchKernelGGL((mf_final_mu_kernel<T, O>), dim3(1), dim3(64), 0, s, p, stage);
+        MI_HIP(hipMemcpyAsync(mu, stage, sizeof(O), hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
     }
 }
 
@@ -704,26 +682,15 @@ extern "C" int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *
                                   const void *V0) {
     return guarded([&] {
         MI_REQUIRE(out && cfg && indptr && indices && data && U0 && V0, "NULL argument");
-        MI_REQUIRE(n_users > 0 && n_items > 0, "empty URM");
-        MI_REQUIRE(cfg->algorithm >= MI355REC_MF_BPR && cfg->algorithm <= MI355REC_MF_ASY_SVD,
-                   "Value for 'algorithm_name' not recognized (%d)", cfg->algorithm);
-        const bool asy = cfg->algorithm == MI355REC_MF_ASY_SVD;
-        MI_REQUIRE(!asy || cfg->batch_size == 1, "Batch size other than 1 not supported for ASY_SVD");
-        if (asy && cfg->n_factors > ASY_KMAX)
-            fail(MI355REC_E_UNSUPPORTED, "ASY_SVD: n_factors = %d exceeds %d", cfg->n_factors, ASY_KMAX);
-        MI_REQUIRE(cfg->sgd_mode >= MI355REC_SGD && cfg->sgd_mode <= MI355REC_ADAM, "Value for 'sgd_mode' not recognized (%d)",
-                   cfg->sgd_mode);
-        MI_REQUIRE(cfg->n_factors >= 1, "n_factors must be >= 1");
-        if (cfg->n_factors > 512) fail(MI355REC_E_UNSUPPORTED, "n_factors = %d exceeds 512", cfg->n_factors);
-        MI_REQUIRE(cfg->batch_size >= 1, "batch_size must be >= 1");
-        MI_REQUIRE(cfg->precision == MI355REC_F32 || cfg->precision == MI355REC_F64, "precision must be MI355REC_F32 or MI355REC_F64");
+        check_config(cfg, n_users, n_items);
+        const MfKnobs knobs = read_mf_knobs();
         ensure_device();
         std::unique_ptr<mi355rec_mf> h(new mi355rec_mf());
         h->cfg = *cfg;
         h->n_users = n_users;
         h->n_items = n_items;
         h->k = cfg->n_factors;
-        h->n_u_rows = asy ? n_items : n_users;
+        h->n_u_rows = cfg->algorithm == MI355REC_MF_ASY_SVD ? n_items : n_users;
         h->f64 = cfg->precision == MI355REC_F64;
         h->nnz = (size_t)indptr[n_users];
         MI_REQUIRE(h->nnz > 0, "URM has no interactions");
@@ -733,20 +700,7 @@ extern "C" int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *
         h->indices.upload(indices, h->nnz, s);
         h->data.upload(data, h->nnz, s);
         if (h->f64) create_typed<double>(h.get(), U0, V0); else create_typed<float>(h.get(), U0, V0);
-        h->par.alloc_zero((size_t)n_users + n_items, s);
-        if (getenv("MI355REC_MF_TICKS")) {
-            h->ticks.alloc_zero((size_t)per_sample(h.get()) * cfg->batch_size * 8, s);
-            h->sched_ticks.alloc_zero((size_t)FAST_MAX_BATCHES * SCHED_STAMPS, s);
-        }
-        h->loss_slots.alloc_zero((size_t)per_sample(h.get()) * cfg->batch_size * 4, s);
-        h->state.alloc_zero(1, s);
-        {   // Adam's running beta powers start at beta^1 (.pyx:217-218)
-            MfState init{};
-            init.beta_1_power = cfg->beta_1;
-            init.beta_2_power = cfg->beta_2;
-            MI_HIP(hipMemcpyAsync(h->state.ptr, &init, sizeof(MfState), hipMemcpyHostToDevice, s));
-        }
-        MI_HIP(hipStreamSynchronize(s));
+        create_state(h.get(), knobs);
         *out = h.release();
     });
 }
@@ -755,9 +709,10 @@ extern "C" int mi355rec_mf_run_epochs(mi355rec_mf_t h, int32_t n_epochs) {
     return guarded([&] {
         MI_REQUIRE(h, "NULL handle");
         MI_REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
+        const MfKnobs knobs = read_mf_knobs();
         ensure_device();
         ReleaseScope scope(h->stream);
-        if (h->f64) run_epochs_typed<double>(h, n_epochs); else run_epochs_typed<float>(h, n_epochs);
+        if (h->f64) run_epochs_typed<double>(h, knobs, n_epochs); else run_epochs_typed<float>(h, knobs, n_epochs);
     });
 }
 
@@ -768,18 +723,19 @@ extern "C" int mi355rec_mf_run_samples(mi355rec_mf_t h, const int32_t *u, const 
         const bool bpr = h->cfg.algorithm == MI355REC_MF_BPR;
         MI_REQUIRE(bpr ? j != nullptr : rating != nullptr, "%s", bpr ? "BPR replay needs the negative items" : "FunkSVD / AsySVD replay needs the ratings");
         MI_REQUIRE(n >= 0, "n must be >= 0");
+        const MfKnobs knobs = read_mf_knobs();
         ensure_device();
         if (n == 0) return;
         const long long B = h->cfg.batch_size;
-        const long long per_epoch = batches_per_epoch(h);
-        ensure_stream_capacity(h, (size_t)std::max<long long>(n, per_epoch * B), std::max<long long>((n + B - 1) / B, per_epoch));
+        const long long per_epoch = batches_per_epoch(shape_of(h));
+        ensure_stream_capacity(h, knobs, (size_t)std::max<long long>(n, per_epoch * B), std::max<long long>(ceil_div(n, B), per_epoch));
         hipStream_t s = h->stream;
-        MI_HIP(hipMemcpyAsync(h->su.ptr, u, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        MI_HIP(hipMemcpyAsync(h->si.ptr, i, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        if (bpr) MI_HIP(hipMemcpyAsync(h->sj.ptr, j, sizeof(int) * n, hipMemcpyHostToDevice, s));
-        else MI_HIP(hipMemcpyAsync(h->sr.ptr, rating, sizeof(float) * n, hipMemcpyHostToDevice, s));
+        MI_HIP(hipMemcpyAsync(h->buf.su.ptr, u, sizeof(int) * n, hipMemcpyHostToDevice, s));
+        MI_HIP(hipMemcpyAsync(h->buf.si.ptr, i, sizeof(int) * n, hipMemcpyHostToDevice, s));
+        if (bpr) MI_HIP(hipMemcpyAsync(h->buf.sj.ptr, j, sizeof(int) * n, hipMemcpyHostToDevice, s));
+        else MI_HIP(hipMemcpyAsync(h->buf.sr.ptr, rating, sizeof(float) * n, hipMemcpyHostToDevice, s));
         h->last_call_samples = 0;
-        if (h->f64) run_samples_typed<double>(h, n); else run_samples_typed<float>(h, n);
+        if (h->f64) run_samples_typed<double>(h, knobs, n); else run_samples_typed<float>(h, knobs, n);
     });
 }
 
@@ -787,15 +743,15 @@ extern "C" int mi355rec_mf_run_samples(mi355rec_mf_t h, const int32_t *u, const 
 namespace {
 
 template <class T>
-void shard_begin_typed(mi355rec_mf *h) {
-    const long long B = h->cfg.batch_size, per_epoch = batches_per_epoch(h);
-    ensure_stream_capacity(h, (size_t)(per_epoch * B), per_epoch, true);
+void shard_begin_typed(mi355rec_mf *h, const MfKnobs &knobs) {
+    const long long B = h->cfg.batch_size, per_epoch = batches_per_epoch(shape_of(h));
+    ensure_stream_capacity(h, knobs, (size_t)(per_epoch * B), per_epoch, true);
     MfParams<T> p{};
     fill_params(h, p);
     begin_call(h);
     h->timer.start(h->stream);
     launch_sampler(h, p);                                   // the same stream on every rank: the generator is counter based
-    enqueue_schedule(h, p.samples_per_epoch, per_epoch);
+    enqueue_schedule(h, knobs, p.samples_per_epoch, per_epoch);
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(h->stream));
 }
@@ -804,12 +760,12 @@ template <class T>
 void shard_batch_typed(mi355rec_mf *h, int b) {
     MfParams<T> p{};
     fill_params(h, p);
-    const int wgs = div_up(p.tasks_per_batch, 4);
-    p.wg_base = h->shard_rank;
-    p.wg_stride = h->shard_world;
-    launch_batch<MI355REC_MF_BPR, T>(h, p, b, true, wgs > h->shard_rank ? (wgs - h->shard_rank + h->shard_world - 1) / h->shard_world : 0);
-    hipLaunchKernelGGL((mf_shard_rows_kernel<T, true>), dim3(wgs), dim3(256), 0, h->stream, p, b, h->shard_rank, h->shard_world,
-                       h->shard_slots_per_rank, as<T>(h->shard_send));
+    const ShardPlan sh = shard_plan(shape_of(h), p.tasks_per_batch, h->shard.rank, h->shard.world);
+    p.wg_base = h->shard.rank;
+    p.wg_stride = h->shard.world;
+    launch_batch<MI355REC_MF_BPR, T>(h, p, b, true, sh.rank_wgs);
+    hipLaunchKernelGGL((mf_shard_rows_kernel<T, true>), dim3(sh.wgs), dim3(256), 0, h->stream, p, b, h->shard.rank, h->shard.world,
+                       h->shard.slots_per_rank, as<T>(h->shard.send));
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(h->stream));                // the caller's collective may run on any stream
 }
@@ -818,22 +774,23 @@ template <class T>
 void shard_merge_typed(mi355rec_mf *h, int b) {
     MfParams<T> p{};
     fill_params(h, p);
-    hipLaunchKernelGGL((mf_shard_rows_kernel<T, false>), dim3(div_up(p.tasks_per_batch, 4)), dim3(256), 0, h->stream, p, b, h->shard_rank,
-                       h->shard_world, h->shard_slots_per_rank, as<T>(h->shard_recv));
+    hipLaunchKernelGGL((mf_shard_rows_kernel<T, false>), dim3(div_up(p.tasks_per_batch, 4)), dim3(256), 0, h->stream, p, b, h->shard.rank,
+                       h->shard.world, h->shard.slots_per_rank, as<T>(h->shard.recv));
     MI_HIP(hipGetLastError());
     MI_HIP(hipStreamSynchronize(h->stream));                // the slab may be overwritten by the next exchange
 }
 
 template <class T>
 void shard_end_typed(mi355rec_mf *h) {
-    const long long B = h->cfg.batch_size, per_epoch = batches_per_epoch(h);
+    const MfShape s = shape_of(h);
+    const long long B = h->cfg.batch_size, per_epoch = batches_per_epoch(s);
     MfParams<T> p{};
     fill_params(h, p);
     hipLaunchKernelGGL(mf_stream_end_kernel<T>, dim3(1), dim3(64), 0, h->stream, p, per_epoch);
     h->timer.stop(h->stream);
     h->batches_done += per_epoch;
     h->last_call_samples = per_epoch * B;
-    finish_call(h, per_epoch * B, per_epoch);               // (the loss is this rank's share)
+    finish_call(h, per_epoch * B, n_launches(s, per_epoch, 1));               // (the loss is this rank's share)
 }
 
 // An error inside an exact multi-GPU epoch ends that epoch: the handle leaves the sharded state, so the next call is refused with
@@ -841,7 +798,7 @@ void shard_end_typed(mi355rec_mf *h) {
 struct ShardEpochGuard {
     mi355rec_mf *h;
     bool ok = false;
-    ~ShardEpochGuard() { if (!ok) h->shard_rank = -1; }
+    ~ShardEpochGuard() { if (!ok) h->shard.rank = -1; }
 };
 
 }  // namespace
@@ -853,31 +810,29 @@ extern "C" int mi355rec_mf_shard_begin_epoch(mi355rec_mf_t h, int32_t rank, int3
         MI_REQUIRE(world >= 1 && rank >= 0 && rank < world, "rank %d of %d", rank, world);
         if (h->cfg.algorithm != MI355REC_MF_BPR || h->cfg.sgd_mode != MI355REC_SGD)
             fail(MI355REC_E_UNSUPPORTED, "the exact multi-GPU mode covers MF_BPR with sgd (optimiser moments and the FunkSVD global bias are not exchanged)");
+        const MfKnobs knobs = read_mf_knobs();
         ensure_device();
-        const int tpb = per_sample(h) * h->cfg.batch_size;
-        const int wgs = div_up(tpb, 4);
+        const ShardPlan sh = shard_plan(shape_of(h), tasks_per_batch(shape_of(h)), rank, world);
         ShardEpochGuard guard{h};
-        h->shard_rank = rank;
-        h->shard_world = world;
-        h->shard_slots_per_rank = div_up(wgs, world) * 4;    // whole workgroups: a wide list's four quarters stay together
-        const size_t ts = h->f64 ? sizeof(double) : sizeof(float);
-        const size_t per_rank = (size_t)h->shard_slots_per_rank * h->k * ts;
-        if (h->shard_send.count < per_rank) h->shard_send.alloc_zero(per_rank, h->stream);
-        if (h->shard_recv.count < per_rank * world) h->shard_recv.alloc_zero(per_rank * world, h->stream);
-        if (h->f64) shard_begin_typed<double>(h); else shard_begin_typed<float>(h);
-        h->shard_batches = batches_per_epoch(h);
-        *d_send = h->shard_send.ptr;
-        *d_recv = h->shard_recv.ptr;
-        *bytes_per_rank = per_rank;
-        *n_batches = (int32_t)h->shard_batches;
+        h->shard.rank = rank;
+        h->shard.world = world;
+        h->shard.slots_per_rank = sh.slots_per_rank;
+        if (h->shard.send.count < sh.bytes_per_rank) h->shard.send.alloc_zero(sh.bytes_per_rank, h->stream);
+        if (h->shard.recv.count < sh.bytes_per_rank * world) h->shard.recv.alloc_zero(sh.bytes_per_rank * world, h->stream);
+        if (h->f64) shard_begin_typed<double>(h, knobs); else shard_begin_typed<float>(h, knobs);
+        h->shard.batches = batches_per_epoch(shape_of(h));
+        *d_send = h->shard.send.ptr;
+        *d_recv = h->shard.recv.ptr;
+        *bytes_per_rank = sh.bytes_per_rank;
+        *n_batches = (int32_t)h->shard.batches;
         guard.ok = true;
     });
 }
 
 extern "C" int mi355rec_mf_shard_batch(mi355rec_mf_t h, int32_t batch) {
     return guarded([&] {
-        MI_REQUIRE(h && h->shard_rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
-        MI_REQUIRE(batch >= 0 && batch < h->shard_batches, "mini-batch %d of %lld", batch, h->shard_batches);
+        MI_REQUIRE(h && h->shard.rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
+        MI_REQUIRE(batch >= 0 && batch < h->shard.batches, "mini-batch %d of %lld", batch, h->shard.batches);
         ensure_device();
         ShardEpochGuard guard{h};
         if (h->f64) shard_batch_typed<double>(h, batch); else shard_batch_typed<float>(h, batch);
@@ -887,8 +842,8 @@ extern "C" int mi355rec_mf_shard_batch(mi355rec_mf_t h, int32_t batch) {
 
 extern "C" int mi355rec_mf_shard_merge(mi355rec_mf_t h, int32_t batch) {
     return guarded([&] {
-        MI_REQUIRE(h && h->shard_rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
-        MI_REQUIRE(batch >= 0 && batch < h->shard_batches, "mini-batch %d of %lld", batch, h->shard_batches);
+        MI_REQUIRE(h && h->shard.rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
+        MI_REQUIRE(batch >= 0 && batch < h->shard.batches, "mini-batch %d of %lld", batch, h->shard.batches);
         ensure_device();
         ShardEpochGuard guard{h};
         if (h->f64) shard_merge_typed<double>(h, batch); else shard_merge_typed<float>(h, batch);
@@ -898,7 +853,7 @@ extern "C" int mi355rec_mf_shard_merge(mi355rec_mf_t h, int32_t batch) {
 
 extern "C" int mi355rec_mf_shard_end_epoch(mi355rec_mf_t h) {
     return guarded([&] {
-        MI_REQUIRE(h && h->shard_rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
+        MI_REQUIRE(h && h->shard.rank >= 0, "mi355rec_mf_shard_begin_epoch has not been called");
         ensure_device();
         ShardEpochGuard guard{h};                            // (ends the sharded state on success too)
         if (h->f64) shard_end_typed<double>(h); else shard_end_typed<float>(h);
@@ -909,7 +864,7 @@ extern "C" int mi355rec_mf_shard_end_epoch(mi355rec_mf_t h) {
 struct mi355rec_mf_group : Handle {
     std::vector<mi355rec_mf *> members;      // not owned
     bool f64 = false;
-    int algorithm = 0, klass = 0, tasks_per_batch = 0;
+    int algorithm = 0, klass = 0, tasks_per_batch = 0;      // klass: position of the shared instance in mf_plan.h's RowWidths
     bool plain_sgd = false;                 // every member runs sgd_mode "sgd"
     long long batches_per_epoch = 0;
     int max_timed = 0;
@@ -936,11 +891,15 @@ struct mi355rec_mf_group : Handle {
     hipGraphExec_t graph = nullptr;
     bool graph_failed = false;
 
+    void drop_graph() {
+        if (graph) (void)hipGraphExecDestroy(graph);
+        graph = nullptr;
+    }
     ~mi355rec_mf_group() {
         shutdown([&] {
             if (ahead_fork) (void)hipEventDestroy(ahead_fork);
             if (ahead_join) (void)hipEventDestroy(ahead_join);
-            if (graph) (void)hipGraphExecDestroy(graph);
+            drop_graph();
             if (fork) (void)hipEventDestroy(fork);
             for (auto e : join) (void)hipEventDestroy(e);
         });
@@ -949,8 +908,9 @@ struct mi355rec_mf_group : Handle {
 
 namespace {
 
-// One epoch of every member: samplers and schedules on the members' own streams (parallel branches, also when captured), then
-// the shared chain of mini-batch launches on the group's stream.
+template <class T>
+const MfParams<T> *params_table(const DeviceBuffer<unsigned char> &table) { return reinterpret_cast<const MfParams<T> *>(table.ptr); }
+
 // sampler + schedule of all members (all on the in-LDS schedule): four launches
 template <class T>
 void group_enqueue_schedule(mi355rec_mf_group *g, const MfParams<T> *table, const FastSchedParams *sched_table, hipStream_t s) {
@@ -966,7 +926,7 @@ void group_enqueue_schedule(mi355rec_mf_group *g, const MfParams<T> *table, cons
     set_sched_sort_attribute(reinterpret_cast<const void *>(mf_group_sched_sort_kernel), attr_set);
     int max_entries = 0;
     for (const auto &f : g->host_sched_table) max_entries = std::max(max_entries, f.n_entries);
-    hipLaunchKernelGGL(mf_group_sched_sort_kernel, dim3((unsigned)nb, R), dim3(SCHED_THREADS), sched_lds_bytes(f0.np), s, sched_table);
+    hipLaunchKernelGGL(mf_group_sched_sort_kernel, dim3((unsigned)nb, R), dim3(SCHED_THREADS), sched_lds(f0.np), s, sched_table);
     hipLaunchKernelGGL(mf_group_sched_emit_kernel, dim3(div_up(f0.batch_size, 256), (unsigned)nb, R), dim3(256), 0, s, sched_table);
     hipLaunchKernelGGL(mf_group_sched_finish_kernel, dim3(div_up(max_entries, 256), R), dim3(256), 0, s, sched_table);
 }
@@ -975,8 +935,7 @@ void group_enqueue_schedule(mi355rec_mf_group *g, const MfParams<T> *table, cons
 template <class T>
 void group_enqueue_batches(mi355rec_mf_group *g, const MfParams<T> *table, bool timed) {
     const long long nb = g->batches_per_epoch;
-    // a third of the slots' workgroups: the kernel loops over the slots in use (all of them when a member is on the general schedule)
-    const int wgs = div_up(div_up(g->tasks_per_batch, 4), 3), R = (int)g->members.size();
+    const int wgs = group_workgroups(g->tasks_per_batch), R = (int)g->members.size();
     for (long long b = 0; b < nb; ++b) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) g->dispatch_timers.next(e0, e1, g->max_timed);
@@ -986,12 +945,9 @@ void group_enqueue_batches(mi355rec_mf_group *g, const MfParams<T> *table, bool 
     hipLaunchKernelGGL(mf_group_stream_end_kernel<T>, dim3(div_up(R, 64)), dim3(64), 0, g->stream, table, R, nb);
 }
 
+// samplers and schedules on the members' own streams (parallel branches, also when captured)
 template <class T>
-void group_enqueue_epoch(mi355rec_mf_group *g, bool timed) {
-    const long long nb = g->batches_per_epoch;
-    if (g->all_fast) {
-        group_enqueue_schedule<T>(g, reinterpret_cast<const MfParams<T> *>(g->table.ptr), g->sched_table.ptr, g->stream);
-    } else {
+void group_enqueue_member_schedules(mi355rec_mf_group *g, const MfKnobs &knobs) {
     MI_HIP(hipEventRecord(g->fork, g->stream));
     for (size_t m = 0; m < g->members.size(); ++m) {
         mi355rec_mf *h = g->members[m];
@@ -999,75 +955,65 @@ void group_enqueue_epoch(mi355rec_mf_group *g, bool timed) {
         MfParams<T> p{};
         fill_params(h, p);
         launch_sampler(h, p);
-        enqueue_schedule(h, p.samples_per_epoch, nb);
+        enqueue_schedule(h, knobs, p.samples_per_epoch, g->batches_per_epoch);
         MI_HIP(hipEventRecord(g->join[m], h->stream));
         MI_HIP(hipStreamWaitEvent(g->stream, g->join[m], 0));
     }
-    }
-    group_enqueue_batches<T>(g, reinterpret_cast<const MfParams<T> *>(g->table.ptr), timed);
 }
 
+// One epoch of every member: sampler and schedule, then the shared chain of mini-batch launches on the group's stream.
 template <class T>
-void group_ensure_graph(mi355rec_mf_group *g) {
-    if (g->graph || g->graph_failed) return;
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        try {
-            group_enqueue_epoch<T>(g, false);
-        } catch (...) {
-            (void)hipStreamEndCapture(g->stream, &graph);
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-            g->graph_failed = true;
-            return;
-        }
-        e = hipStreamEndCapture(g->stream, &graph);
-    }
-    if (e == hipSuccess) e = hipGraphInstantiate(&g->graph, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        g->graph = nullptr;
-        g->graph_failed = true;
-    }
+void group_enqueue_epoch(mi355rec_mf_group *g, const MfKnobs &knobs, bool timed) {
+    if (g->all_fast) group_enqueue_schedule<T>(g, params_table<T>(g->table), g->sched_table.ptr, g->stream);
+    else group_enqueue_member_schedules<T>(g, knobs);
+    group_enqueue_batches<T>(g, params_table<T>(g->table), timed);
 }
 
+// Stage 1: every member's buffers and parameter block, as the bytes of MfParams<T>[R].
 template <class T>
-void group_run_epochs_typed(mi355rec_mf_group *g, int n_epochs) {
+std::vector<unsigned char> group_member_table(mi355rec_mf_group *g, const MfKnobs &knobs) {
     const long long nb = g->batches_per_epoch;
     const int R = (int)g->members.size();
     std::vector<unsigned char> table(sizeof(MfParams<T>) * (size_t)R);
     for (int m = 0; m < R; ++m) {
         mi355rec_mf *h = g->members[m];
-        MI_REQUIRE(h->shard_rank < 0, "member %d is inside an exact multi-GPU epoch", m);
-        ensure_stream_capacity(h, (size_t)(nb * h->cfg.batch_size), nb, true);
+        MI_REQUIRE(h->shard.rank < 0, "member %d is inside an exact multi-GPU epoch", m);
+        ensure_stream_capacity(h, knobs, (size_t)(nb * h->cfg.batch_size), nb, true);
         MfParams<T> p;
         memset(&p, 0, sizeof(p));
         fill_params(h, p);
+        p.used = reads_used_slots(shape_of(h), knobs) ? h->lds.used.ptr : nullptr;
         memcpy(table.data() + sizeof(MfParams<T>) * (size_t)m, &p, sizeof(MfParams<T>));
         begin_call(h);
         MI_HIP(hipStreamSynchronize(h->stream));      // (its clears and first-touch memsets run on the member's own stream)
     }
-    std::vector<FastSchedParams> sched((size_t)R);
-    bool all_fast = !getenv("MI355REC_MF_GROUP_PER_MEMBER_SCHEDULE");
-    for (int m = 0; m < R; ++m) {
+    return table;
+}
+
+// Stage 2: the members' in-LDS schedule tables; `all_fast` says whether every member is on that schedule (the tables of the members
+// in front of the first one that is not are filled, as ever: the change detection below compares them only when all_fast).
+std::vector<FastSchedParams> group_sched_table(mi355rec_mf_group *g, const MfKnobs &knobs, bool &all_fast) {
+    const long long nb = g->batches_per_epoch;
+    std::vector<FastSchedParams> sched(g->members.size());
+    all_fast = !knobs.group_per_member_schedule;
+    for (size_t m = 0; m < g->members.size(); ++m) {
         mi355rec_mf *h = g->members[m];
-        all_fast = all_fast && h->fast_schedule && fast_schedule_fits(h, nb);
-        if (all_fast) {
-            sched[m] = fast_sched_params(h, nb * (long long)h->cfg.batch_size);
-            // (the group's mini-batch kernel reads `used` and never looks at a slot past the last workgroup in use: two thirds of the
-            // header slots of a fused BPR mini-batch are not zero-filled -- 150 MB of 16-byte stores per 32-model epoch)
-            sched[m].fill_all = 0;
-        }
+        all_fast = all_fast && runs_fast_schedule(shape_of(h), knobs, nb);
+        if (!all_fast) continue;
+        sched[m] = fast_sched_params(h, knobs, nb * (long long)h->cfg.batch_size);
+        // (the group's mini-batch kernel reads `used` and never looks at a slot past the last workgroup in use: two thirds of the
+        // header slots of a fused BPR mini-batch are not zero-filled -- 150 MB of 16-byte stores per 32-model epoch)
+        sched[m].fill_all = 0;
     }
+    return sched;
+}
+
+// Stage 3: what changed since the last call goes to the device, and the graph that holds the old addresses goes away.
+void group_publish_tables(mi355rec_mf_group *g, const std::vector<unsigned char> &table, const std::vector<FastSchedParams> &sched, bool all_fast) {
     const bool sched_changed = all_fast != g->all_fast || (all_fast && (g->host_sched_table.size() != sched.size() ||
                                memcmp(g->host_sched_table.data(), sched.data(), sizeof(FastSchedParams) * sched.size()) != 0));
     if (sched_changed) {
-        if (g->graph) {
-            (void)hipGraphExecDestroy(g->graph);
-            g->graph = nullptr;
-        }
+        g->drop_graph();
         MI_HIP(hipStreamSynchronize(g->stream));
         g->all_fast = all_fast;
         g->host_sched_table = sched;
@@ -1076,115 +1022,160 @@ void group_run_epochs_typed(mi355rec_mf_group *g, int n_epochs) {
             MI_HIP(hipMemcpy(g->sched_table.ptr, sched.data(), sizeof(FastSchedParams) * sched.size(), hipMemcpyHostToDevice));
         }
     }
-    if (table != g->host_table) {                 // a member re-allocated its stream buffers: the graph holds the old addresses
-        if (g->graph) {
-            (void)hipGraphExecDestroy(g->graph);
-            g->graph = nullptr;
-        }
+    if (table != g->host_table) {                 // a member re-allocated its stream buffers
+        g->drop_graph();
         MI_HIP(hipStreamSynchronize(g->stream));
         if (g->table.count < table.size()) g->table.alloc(table.size());
         MI_HIP(hipMemcpy(g->table.ptr, table.data(), table.size(), hipMemcpyHostToDevice));
         g->host_table = table;
     }
-    g->dispatch_timers.reset();
-    const long long timed_epochs = g->max_timed > 0 ? std::min<long long>(n_epochs, (g->max_timed + nb - 1) / nb) : 0;
-    const bool ahead = g->all_fast && n_epochs > 1 && !getenv("MI355REC_MF_GROUP_NO_LOOKAHEAD");
-    bool use_graph = !ahead && nb <= GRAPH_SEGMENT && n_epochs - timed_epochs > 0 && !getenv("MI355REC_NO_GRAPH");
-    if (use_graph) {
-        group_ensure_graph<T>(g);
-        use_graph = g->graph != nullptr;
+}
+
+// Stage 4 (look-ahead only): set B (once per group, again when a member's buffers moved) ...
+void group_ensure_set_b(mi355rec_mf_group *g) {
+    const size_t R = g->members.size();
+    bool fresh = g->set_b.size() != R;
+    for (size_t m = 0; m < R && !fresh; ++m) {
+        const mi355rec_mf *h = g->members[m];
+        const mi355rec_mf_group::SetB &b = *g->set_b[m];
+        fresh = b.tasks.count != h->buf.tasks.count || b.recs.count != h->buf.recs.count || b.slot_recs.count != h->buf.slot_recs.count ||
+                b.used.count != h->lds.used.count;
     }
-    if (ahead) {
-        // set B and its tables (once per group, again when a member's buffers moved)
-        bool fresh = g->set_b.size() != (size_t)R;
-        for (int m = 0; m < R && !fresh; ++m) {
-            const mi355rec_mf *h = g->members[m];
-            const mi355rec_mf_group::SetB &b = *g->set_b[m];
-            fresh = b.tasks.count != h->tasks.count || b.recs.count != h->recs.count || b.slot_recs.count != h->slot_recs.count || b.used.count != h->used.count;
-        }
-        if (fresh) {
-            MI_HIP(hipStreamSynchronize(g->stream));
-            g->open_side();
-            if (!g->ahead_fork) MI_HIP(hipEventCreateWithFlags(&g->ahead_fork, hipEventDisableTiming));
-            if (!g->ahead_join) MI_HIP(hipEventCreateWithFlags(&g->ahead_join, hipEventDisableTiming));
-            g->set_b.clear();
-            for (int m = 0; m < R; ++m) {
-                mi355rec_mf *h = g->members[m];
-                std::unique_ptr<mi355rec_mf_group::SetB> b(new mi355rec_mf_group::SetB());
-                b->tasks.alloc_zero(h->tasks.count, g->stream);
-                b->recs.alloc(h->recs.count);
-                b->slot_recs.alloc_zero(h->slot_recs.count, g->stream);
-                b->used.alloc(h->used.count);
-                g->set_b.push_back(std::move(b));
-            }
-        }
-        std::vector<unsigned char> table_b = table;
-        std::vector<FastSchedParams> sched_b = sched;
-        for (int m = 0; m < R; ++m) {
-            MfParams<T> pb;
-            memcpy(&pb, table_b.data() + sizeof(MfParams<T>) * (size_t)m, sizeof(pb));
-            const mi355rec_mf_group::SetB &b = *g->set_b[m];
-            pb.tasks = b.tasks.ptr; pb.recs = b.recs.ptr; pb.slot_recs = b.slot_recs.ptr; pb.used = b.used.ptr;
-            memcpy(table_b.data() + sizeof(MfParams<T>) * (size_t)m, &pb, sizeof(pb));
-            sched_b[m].tasks = b.tasks.ptr; sched_b[m].recs = b.recs.ptr; sched_b[m].slot_recs = b.slot_recs.ptr; sched_b[m].used = b.used.ptr;
-        }
-        if (g->table_b.count < table_b.size()) g->table_b.alloc(table_b.size());
-        if (g->sched_table_b.count < sched_b.size()) g->sched_table_b.alloc(sched_b.size());
-        MI_HIP(hipMemcpyAsync(g->table_b.ptr, table_b.data(), table_b.size(), hipMemcpyHostToDevice, g->stream));
-        MI_HIP(hipMemcpyAsync(g->sched_table_b.ptr, sched_b.data(), sizeof(FastSchedParams) * sched_b.size(), hipMemcpyHostToDevice, g->stream));
-        MI_HIP(hipStreamSynchronize(g->stream));           // (the two vectors are locals)
-    }
-    g->timer.start(g->stream);
-    if (ahead) {
-        const MfParams<T> *tab[2] = {reinterpret_cast<const MfParams<T> *>(g->table.ptr), reinterpret_cast<const MfParams<T> *>(g->table_b.ptr)};
-        const FastSchedParams *sch[2] = {g->sched_table.ptr, g->sched_table_b.ptr};
-        group_enqueue_schedule<T>(g, tab[0], sch[0], g->stream);                   // the call's first epoch: nothing to hide it behind
-        for (long long e = 0; e < n_epochs; ++e) {
-            const int cur = (int)(e & 1);
-            if (e + 1 < n_epochs) {
-                MI_HIP(hipEventRecord(g->ahead_fork, g->stream));                   // (behind epoch e's schedule and epoch e - 1's mini-batches)
-                MI_HIP(hipStreamWaitEvent(g->side, g->ahead_fork, 0));
-                group_enqueue_schedule<T>(g, tab[cur ^ 1], sch[cur ^ 1], g->side);
-                MI_HIP(hipEventRecord(g->ahead_join, g->side));
-            }
-            group_enqueue_batches<T>(g, tab[cur], e < timed_epochs);
-            if (e + 1 < n_epochs) MI_HIP(hipStreamWaitEvent(g->stream, g->ahead_join, 0));
-        }
-    } else {
-        for (long long e = 0; e < n_epochs; ++e) {
-            if (e < timed_epochs || !use_graph) group_enqueue_epoch<T>(g, e < timed_epochs);
-            else MI_HIP(hipGraphLaunch(g->graph, g->stream));
-        }
-    }
-    g->timer.stop(g->stream);
-    MI_HIP(hipGetLastError());
+    if (!fresh) return;
     MI_HIP(hipStreamSynchronize(g->stream));
+    g->open_side();
+    if (!g->ahead_fork) MI_HIP(hipEventCreateWithFlags(&g->ahead_fork, hipEventDisableTiming));
+    if (!g->ahead_join) MI_HIP(hipEventCreateWithFlags(&g->ahead_join, hipEventDisableTiming));
+    g->set_b.clear();
+    for (const mi355rec_mf *h : g->members) {
+        std::unique_ptr<mi355rec_mf_group::SetB> b(new mi355rec_mf_group::SetB());
+        b->tasks.alloc_zero(h->buf.tasks.count, g->stream);
+        b->recs.alloc(h->buf.recs.count);
+        b->slot_recs.alloc_zero(h->buf.slot_recs.count, g->stream);
+        b->used.alloc(h->lds.used.count);
+        g->set_b.push_back(std::move(b));
+    }
+}
+
+// ... and its tables: the A tables with the four pointers swapped
+template <class T>
+void group_publish_tables_b(mi355rec_mf_group *g, std::vector<unsigned char> table_b, std::vector<FastSchedParams> sched_b) {
+    for (size_t m = 0; m < g->members.size(); ++m) {
+        MfParams<T> pb;
+        memcpy(&pb, table_b.data() + sizeof(MfParams<T>) * m, sizeof(pb));
+        const mi355rec_mf_group::SetB &b = *g->set_b[m];
+        pb.tasks = b.tasks.ptr; pb.recs = b.recs.ptr; pb.slot_recs = b.slot_recs.ptr; pb.used = b.used.ptr;
+        memcpy(table_b.data() + sizeof(MfParams<T>) * m, &pb, sizeof(pb));
+        sched_b[m].tasks = b.tasks.ptr; sched_b[m].recs = b.recs.ptr; sched_b[m].slot_recs = b.slot_recs.ptr; sched_b[m].used = b.used.ptr;
+    }
+    if (g->table_b.count < table_b.size()) g->table_b.alloc(table_b.size());
+    if (g->sched_table_b.count < sched_b.size()) g->sched_table_b.alloc(sched_b.size());
+    MI_HIP(hipMemcpyAsync(g->table_b.ptr, table_b.data(), table_b.size(), hipMemcpyHostToDevice, g->stream));
+    MI_HIP(hipMemcpyAsync(g->sched_table_b.ptr, sched_b.data(), sizeof(FastSchedParams) * sched_b.size(), hipMemcpyHostToDevice, g->stream));
+    MI_HIP(hipStreamSynchronize(g->stream));           // (the two vectors are locals)
+}
+
+// Stage 5, look-ahead: epoch e + 1's schedule on `side` beside epoch e's mini-batches, the two table sets in turn
+template <class T>
+void group_run_ahead(mi355rec_mf_group *g, long long n_epochs, long long timed) {
+    const MfParams<T> *tab[2] = {params_table<T>(g->table), params_table<T>(g->table_b)};
+    const FastSchedParams *sch[2] = {g->sched_table.ptr, g->sched_table_b.ptr};
+    group_enqueue_schedule<T>(g, tab[0], sch[0], g->stream);                   // the call's first epoch: nothing to hide it behind
+    for (long long e = 0; e < n_epochs; ++e) {
+        const int cur = (int)(e & 1);
+        if (e + 1 < n_epochs) {
+            MI_HIP(hipEventRecord(g->ahead_fork, g->stream));                   // (behind epoch e's schedule and epoch e - 1's mini-batches)
+            MI_HIP(hipStreamWaitEvent(g->side, g->ahead_fork, 0));
+            group_enqueue_schedule<T>(g, tab[cur ^ 1], sch[cur ^ 1], g->side);
+            MI_HIP(hipEventRecord(g->ahead_join, g->side));
+        }
+        group_enqueue_batches<T>(g, tab[cur], e < timed);
+        if (e + 1 < n_epochs) MI_HIP(hipStreamWaitEvent(g->stream, g->ahead_join, 0));
+    }
+}
+
+// Stage 5, otherwise: timed epochs as plain launches, the rest replays one graph (captured once per group) or plain launches, too
+template <class T>
+bool group_ensure_graph(mi355rec_mf_group *g, const MfKnobs &knobs) {
+    if (!g->graph && !g->graph_failed) {
+        g->graph = capture_graph(g->stream, [&] { group_enqueue_epoch<T>(g, knobs, false); });
+        g->graph_failed = g->graph == nullptr;
+    }
+    return g->graph != nullptr;
+}
+
+template <class T>
+void group_run_plain(mi355rec_mf_group *g, const MfKnobs &knobs, long long n_epochs, long long timed, bool graph) {
+    for (long long e = 0; e < n_epochs; ++e) {
+        if (e < timed || !graph) group_enqueue_epoch<T>(g, knobs, e < timed);
+        else MI_HIP(hipGraphLaunch(g->graph, g->stream));
+    }
+}
+
+// Stage 6: the group's stats and every member's
+void group_account(mi355rec_mf_group *g, long long n_epochs) {
+    const long long nb = g->batches_per_epoch;
     mi355rec_stats &st = g->stats;
     st = mi355rec_stats{};
     st.call_ms = g->timer.elapsed_ms();
     st.kernel_ms = g->dispatch_timers.total_ms();
     st.n_timed = g->dispatch_timers.used;
     st.n_launches = nb * n_epochs;
-    for (int m = 0; m < R; ++m) {
-        mi355rec_mf *h = g->members[m];
+    for (mi355rec_mf *h : g->members) {
         const long long n = nb * n_epochs * (long long)h->cfg.batch_size;
-        h->host_loss.resize(h->loss_slots.count);
-        h->loss_slots.download(h->host_loss.data(), h->loss_slots.count, h->stream);
-        MI_HIP(hipStreamSynchronize(h->stream));
-        double loss = 0;
-        for (double v : h->host_loss) loss += v;
+        const double loss = read_loss(h);
         h->batches_done += nb * n_epochs;
         h->last_call_samples = n_epochs > 0 ? nb * (long long)h->cfg.batch_size : 0;
         h->stats = mi355rec_stats{};
         h->stats.call_ms = st.call_ms;
         h->stats.n_launches = st.n_launches;
         h->stats.n_units = n;
-        h->stats.algorithmic_bytes = bytes_per_sample(h) * (double)n;
+        h->stats.algorithmic_bytes = bytes_per_sample(shape_of(h)) * (double)n;
         h->stats.loss = loss;
         st.n_units += n;
         st.algorithmic_bytes += h->stats.algorithmic_bytes;
         st.loss += loss;
     }
+}
+
+template <class T>
+void group_run_epochs_typed(mi355rec_mf_group *g, const MfKnobs &knobs, int n_epochs) {
+    const long long nb = g->batches_per_epoch;
+    bool all_fast = false;
+    const std::vector<unsigned char> table = group_member_table<T>(g, knobs);
+    const std::vector<FastSchedParams> sched = group_sched_table(g, knobs, all_fast);
+    group_publish_tables(g, table, sched, all_fast);
+    g->dispatch_timers.reset();
+    const long long timed = timed_epochs(g->max_timed, nb, n_epochs);
+    const bool ahead = group_ahead(g->all_fast, n_epochs, knobs);
+    bool graph = group_use_graph(ahead, knobs, nb, n_epochs, timed);
+    if (ahead) {
+        group_ensure_set_b(g);
+        group_publish_tables_b<T>(g, table, sched);
+    } else if (graph) {
+        graph = group_ensure_graph<T>(g, knobs);
+    }
+    g->timer.start(g->stream);
+    if (ahead) group_run_ahead<T>(g, n_epochs, timed);
+    else group_run_plain<T>(g, knobs, n_epochs, timed, graph);
+    g->timer.stop(g->stream);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(g->stream));
+    group_account(g, n_epochs);
+}
+
+// the group's shared numbers come from member 0
+void group_adopt_first(mi355rec_mf_group *g, const mi355rec_mf *first) {
+    const MfShape s = shape_of(first);
+    if (s.algorithm == MI355REC_MF_ASY_SVD) fail(MI355REC_E_UNSUPPORTED, "ASY_SVD has no mini-batches to share a launch");
+    g->f64 = s.f64;
+    g->algorithm = s.algorithm;
+    g->klass = row_width(s.k, s.f64).klass;
+    if (g->klass < 0)
+        fail(MI355REC_E_UNSUPPORTED, "n_factors = %d runs on the any-k kernel, which has no replica-batched form (use a multiple of %d up to %d)",
+             s.k, vec_of(s.f64), widest_chunks(RowWidths{}) * vec_of(s.f64));
+    g->tasks_per_batch = tasks_per_batch(s);
+    g->batches_per_epoch = batches_per_epoch(s);
 }
 
 }  // namespace
@@ -1195,30 +1186,20 @@ extern "C" int mi355rec_mf_group_create(mi355rec_mf_group_t *out, const mi355rec
         MI_REQUIRE(n_members >= 1 && n_members <= 65535, "n_members = %d out of range", n_members);
         ensure_device();
         std::unique_ptr<mi355rec_mf_group> g(new mi355rec_mf_group());
-        const mi355rec_mf *first = members[0];
-        MI_REQUIRE(first, "member 0 is NULL");
-        if (first->cfg.algorithm == MI355REC_MF_ASY_SVD) fail(MI355REC_E_UNSUPPORTED, "ASY_SVD has no mini-batches to share a launch");
-        g->f64 = first->f64;
-        g->algorithm = first->cfg.algorithm;
-        g->klass = kernel_class(first);
-        if (g->klass < 0)
-            fail(MI355REC_E_UNSUPPORTED, "n_factors = %d runs on the any-k kernel, which has no replica-batched form (use a multiple of %d up to 512)",
-                 first->k, first->f64 ? 2 : 4);
-        g->tasks_per_batch = per_sample(first) * first->cfg.batch_size;
-        g->batches_per_epoch = batches_per_epoch(first);
+        MI_REQUIRE(members[0], "member 0 is NULL");
+        group_adopt_first(g.get(), members[0]);
+        g->plain_sgd = true;
         for (int m = 0; m < n_members; ++m) {
             mi355rec_mf *h = members[m];
             MI_REQUIRE(h, "member %d is NULL", m);
             for (int o = 0; o < m; ++o) MI_REQUIRE(members[o] != h, "member %d is listed twice", m);
-            // what ONE launch must share: the kernel instance and the grid; everything else is per model
-            MI_REQUIRE(h->cfg.algorithm == g->algorithm && h->f64 == g->f64 && kernel_class(h) == g->klass,
+            const GroupMismatch mismatch = group_mismatch(shape_of(members[0]), shape_of(h));
+            MI_REQUIRE(mismatch != GROUP_OTHER_INSTANCE,
                        "member %d runs a different kernel instance (algorithm, precision or n_factors class) than member 0", m);
-            MI_REQUIRE(per_sample(h) * h->cfg.batch_size == g->tasks_per_batch && batches_per_epoch(h) == g->batches_per_epoch,
-                       "member %d has a different batch_size or number of mini-batches per epoch than member 0", m);
+            MI_REQUIRE(mismatch != GROUP_OTHER_BATCHES, "member %d has a different batch_size or number of mini-batches per epoch than member 0", m);
             g->members.push_back(h);
+            g->plain_sgd = g->plain_sgd && h->cfg.sgd_mode == MI355REC_SGD;
         }
-        g->plain_sgd = true;
-        for (const mi355rec_mf *h : g->members) g->plain_sgd = g->plain_sgd && h->cfg.sgd_mode == MI355REC_SGD;
         g->open(1);
         MI_HIP(hipEventCreateWithFlags(&g->fork, hipEventDisableTiming));
         g->join.resize(n_members, nullptr);
@@ -1231,8 +1212,9 @@ extern "C" int mi355rec_mf_group_run_epochs(mi355rec_mf_group_t g, int32_t n_epo
     return guarded([&] {
         MI_REQUIRE(g, "NULL handle");
         MI_REQUIRE(n_epochs >= 0, "n_epochs must be >= 0");
+        const MfKnobs knobs = read_mf_knobs();
         ensure_device();
-        if (g->f64) group_run_epochs_typed<double>(g, n_epochs); else group_run_epochs_typed<float>(g, n_epochs);
+        if (g->f64) group_run_epochs_typed<double>(g, knobs, n_epochs); else group_run_epochs_typed<float>(g, knobs, n_epochs);
     });
 }
 
@@ -1274,10 +1256,10 @@ extern "C" int mi355rec_mf_get_last_samples(mi355rec_mf_t h, int32_t *u, int32_t
         *n = h->last_call_samples;
         const size_t m = (size_t)std::min<long long>(cap, h->last_call_samples);
         hipStream_t s = h->stream;
-        if (u) h->su.download(u, m, s);
-        if (i) h->si.download(i, m, s);
-        if (j && h->cfg.algorithm == MI355REC_MF_BPR) h->sj.download(j, m, s);
-        if (rating && h->cfg.algorithm != MI355REC_MF_BPR) h->sr.download(rating, m, s);
+        if (u) h->buf.su.download(u, m, s);
+        if (i) h->buf.si.download(i, m, s);
+        if (j && h->cfg.algorithm == MI355REC_MF_BPR) h->buf.sj.download(j, m, s);
+        if (rating && h->cfg.algorithm != MI355REC_MF_BPR) h->buf.sr.download(rating, m, s);
         MI_HIP(hipStreamSynchronize(s));
     });
 }
@@ -1292,27 +1274,31 @@ extern "C" int mi355rec_mf_set_profiling(mi355rec_mf_t h, int32_t max_timed_laun
     });
 }
 
+namespace {
+
+void copy_ticks(mi355rec_mf *h, const DeviceBuffer<unsigned long long> &ticks, uint64_t *out, int64_t cap, int64_t *n) {
+    MI_REQUIRE(h && n, "NULL argument");
+    ensure_device();
+    *n = (int64_t)ticks.count;
+    if (out && cap > 0) {
+        MI_HIP(hipStreamSynchronize(h->stream));
+        MI_HIP(hipMemcpy(out, ticks.ptr, sizeof(uint64_t) * std::min<size_t>((size_t)cap, ticks.count), hipMemcpyDeviceToHost));
+    }
+}
+
+}  // namespace
+
 extern "C" int mi355rec_mf_get_phase_ticks(mi355rec_mf_t h, uint64_t *out, int64_t cap, int64_t *n) {
     return guarded([&] {
-        MI_REQUIRE(h && n, "NULL argument");
-        ensure_device();
-        *n = (int64_t)h->ticks.count;
-        if (out && cap > 0) {
-            MI_HIP(hipStreamSynchronize(h->stream));
-            MI_HIP(hipMemcpy(out, h->ticks.ptr, sizeof(uint64_t) * std::min<size_t>((size_t)cap, h->ticks.count), hipMemcpyDeviceToHost));
-        }
+        MI_REQUIRE(h, "NULL argument");
+        copy_ticks(h, h->ticks, out, cap, n);
     });
 }
 
 extern "C" int mi355rec_mf_get_schedule_ticks(mi355rec_mf_t h, uint64_t *out, int64_t cap, int64_t *n) {
     return guarded([&] {
-        MI_REQUIRE(h && n, "NULL argument");
-        ensure_device();
-        *n = (int64_t)h->sched_ticks.count;
-        if (out && cap > 0) {
-            MI_HIP(hipStreamSynchronize(h->stream));
-            MI_HIP(hipMemcpy(out, h->sched_ticks.ptr, sizeof(uint64_t) * std::min<size_t>((size_t)cap, h->sched_ticks.count), hipMemcpyDeviceToHost));
-        }
+        MI_REQUIRE(h, "NULL argument");
+        copy_ticks(h, h->lds.ticks, out, cap, n);
     });
 }
 

@@ -1,6 +1,8 @@
 // mf_asy.cuh -- AsySVD: strictly ordered steps on one 1024-thread workgroup.  Included by mf.hip after mf_batch.cuh.
 #pragma once
 
+#include "mf_plan.h"
+
 namespace mi355rec {
 namespace {
 
@@ -13,7 +15,6 @@ namespace {
 // and updates (they come from read-only arrays), the first ASY_ROWS rows of each wavefront stay in registers between the gather
 // and the update, and the loads of a step are issued from clamped addresses in one batch (a load inside a conditional is waited
 // for where its branch ends).  Per step that leaves: one gather round trip (L2), two LDS reductions, the scalar part, the stores.
-constexpr int ASY_KMAX = 256;
 constexpr int ASY_CELLS = 12;    // factors per lane that stay in registers between the gather and the update: C chunks of 64 factors x R rows
 // C = chunks of 64 factors a row needs (1: k <= 64, 2: k <= 128, 4: k <= 256); R = ASY_CELLS / C profile rows per wavefront stay
 // in registers (192 / 96 / 48 rows per step: the mean ML-1M profile has 166; 16 cells spill at float64)

@@ -2,6 +2,8 @@
 // the any-k kernel, the row exchange of the exact multi-GPU mode, the getters' gather kernels.  Included by mf.hip after mf_schedule.cuh.
 #pragma once
 
+#include "mf_plan.h"
+
 namespace mi355rec {
 namespace {
 

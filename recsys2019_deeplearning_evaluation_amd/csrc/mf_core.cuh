@@ -2,6 +2,8 @@
 // the rounding-exact gradient helpers, the sampler (round 4: mf.hip split by stage; one translation unit, see mf.hip).
 #pragma once
 
+#include "mf_plan.h"
+
 namespace mi355rec {
 namespace {
 
@@ -28,11 +30,8 @@ typedef int int8v __attribute__((ext_vector_type(8)));
 constexpr int ROLE_U = 0, ROLE_I = 1;   // 2: negative item
 
 template <class T> struct MuState { T mu, c1, c2, pad; };
-// one L2 atomic per workgroup that carries global-bias terms: atomics on ONE address retire at about 0.2 us each (measured through
-// the batch kernel: 31 per address cost 3 us per mini-batch), so the terms are spread over a wavefront's worth of addresses
-constexpr int MU_SLOTS = 64;
-// (Measured and rejected: no atomics at all -- one cell per workgroup, every wavefront of the next batch folds the ~500 cells in a
-// fixed order, which makes the global bias bit-reproducible -- costs 8 loads per lane and wavefront: 157 ms per FunkSVD epoch at
+// (MU_SLOTS, mf_plan.h: the global-bias terms are spread over a wavefront's worth of addresses.  Measured and rejected: no atomics
+// at all -- one cell per workgroup, every wavefront of the next batch folds the ~500 cells in a fixed order, which makes the global bias bit-reproducible -- costs 8 loads per lane and wavefront: 157 ms per FunkSVD epoch at
 // ML-20M shape against 145 ms with 64 atomic slots and 164 ms with 16.)
 
 template <class T>

@@ -2,6 +2,8 @@
 // (one workgroup per mini-batch; fused and pair tasks, wide lists), stream-end kernels.  Included by mf.hip after mf_core.cuh.
 #pragma once
 
+#include "mf_plan.h"
+
 namespace mi355rec {
 namespace {
 
@@ -128,14 +130,7 @@ __global__ __launch_bounds__(256) void mf_recs_kernel(const SchedParams s) {
 // than two rounds of one wavefront get the 4 wavefronts of a workgroup: 4 aligned headers), and one bit per (row, mini-batch) in a global bitmap;
 // (2) per incidence, the version parity of each of the sample's rows = parity at stream start + number of earlier
 // mini-batches with the row's bit set; (3) per row, the parity after the stream, bitmap cleared for the next one.
-constexpr int META_WIDE = 1 << 30;        // header.meta: bits 0-27 list length, 28-29 quarter, 30 wide, 31 buffer of the own row
-constexpr int SCHED_THREADS = 1024;
-constexpr int SLOT_ABSORBED = 0x3fffffff;   // qtask[] of an incidence whose row is updated by its sample's user task (no header of its own)
-constexpr int FAST_MAX_BATCHES = 256, FAST_MAX_SLOTS = 8192;
-// qtask[] of every other incidence: bits 0-12 the header slot (< FAST_MAX_SLOTS), bits 13-17 the incidence's offset within its run
-// (saturated: the emit kernel asks for offsets 0 .. 4 * group - 1 <= 15 only), bit 29 the run is the first of a pair task, bit 30 wide
-constexpr int QTASK_SLOT_MASK = FAST_MAX_SLOTS - 1, QTASK_OFF_SHIFT = 13, QTASK_OFF_MAX = 31, QTASK_PAIR = 1 << 29;
-constexpr int SCHED_STAMPS = 8;           // per workgroup of the sort kernel: entry, keys, sort, run heads, once-touched flags, slot scans, headers, exit
+// (The limits FAST_MAX_BATCHES / FAST_MAX_SLOTS, the layout of header.meta and of qtask[], SCHED_THREADS and SCHED_STAMPS: mf_plan.h.)
 
 struct FastSchedParams {
     long long n_samples;

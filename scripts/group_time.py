@@ -1,5 +1,5 @@
 """32 BPR-MF models in one launch per mini-batch at the headline shape: epoch time (diagnostics; run on the GPU box).
-Environment switches of the library apply (MI355REC_MF_GROUP_OCC8=1, ...)."""
+Environment switches of the library apply (MI355REC_MF_GROUP_NO_LOOKAHEAD=1, MI355REC_MF_GROUP_PER_MEMBER_SCHEDULE=1, MI355REC_NO_GRAPH=1, ...)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
