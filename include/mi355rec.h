@@ -615,6 +615,19 @@ int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, 
 int mi355rec_spscorer_recommend_candidates(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, const int32_t *cand_indptr,
                                            const int32_t *cand_indices, int32_t cutoff, int32_t remove_seen,
                                            const uint8_t *item_allowed, int32_t *ranked);
+/* The exact mode of the sparse scorer (off after create).  By default a score is a sum of float32 products whose order is decided by
+ * which wavefront wins an LDS (or, for rows beyond 32 256 items, a global) float atomic: near-tied scores can change places between
+ * two calls.  With exact != 0 every score is SciPy's csr @ csr bit for bit: from +0.0f, over the stored cells (m, w) of the user's row
+ * of A IN STORAGE ORDER (A's indices are used as given, never sorted) and, for each, over the stored cells (j, b) of row m of B,
+ * s[j] = s[j] + (w * b) in float32 with the product rounded before the add.  No float atomic runs; the same call gives the same bytes
+ * every time, however a batch is cut into blocks; a candidate's score is the cell of the full row.  It applies to
+ * mi355rec_spscorer_recommend[_candidates] and to mi355rec_eval_add_spscorer[_candidates] alike.
+ * Switching it on runs one device pass over B: every row must hold its column ids strictly ascending inside [0, n_items) (sort B's
+ * indices first; a column stored twice in a row cannot be served).  Otherwise MI355REC_E_INVALID, the message names the first
+ * offending row, the mode is unchanged and the handle stays usable.  exact == 0 switches back to the atomic kernels.
+ * get_stats after an exact recommend: kernel_ms = call_ms = the exact scoring kernel (recommend_candidates: that kernel and the
+ * candidates' gather + ranking). */
+int mi355rec_spscorer_set_exact(mi355rec_spscorer_t h, int32_t exact);
 int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 

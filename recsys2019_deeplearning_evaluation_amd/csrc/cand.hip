@@ -237,6 +237,7 @@ Ranking mi355rec_scorer::enqueue_candidates(const int *users, int n, int cutoff,
 
 Ranking mi355rec_spscorer::enqueue_candidates(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
                                               const CandidateRows &rows) {
+    if (exact) return spexact_enqueue_candidates(this, users, n, cutoff, remove_seen, allowed, rows);
     hipStream_t s = stream;
     check_candidate_cutoff(cutoff);
     const bool in_lds = score_row_fits_lds(n_items, cutoff);

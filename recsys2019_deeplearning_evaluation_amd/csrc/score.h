@@ -87,7 +87,9 @@ struct mi355rec_scorer final : mi355rec::ScorerHandle {      // `timer`: the GEM
 
 struct mi355rec_spscorer final : mi355rec::ScorerHandle {    // `timer`: the scoring dispatch
     int n_mid = 0;
+    int exact = 0;                                   // mi355rec_spscorer_set_exact: both enqueues go through spexact.hip
     mi355rec::DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx;
+    mi355rec::DeviceBuffer<int> cuts;               // exact mode: where every row of B crosses into each slice of a score row
     mi355rec::DeviceBuffer<float> a_val, b_val;
     double nnz_a = 0, nnz_b = 0;
 
@@ -142,6 +144,12 @@ void check_candidate_cutoff(int cutoff);    // a list wider than MAX_TOPK (topk.
 // unfiltered, not ranked; the caller has reserved h->scores.
 bool score_row_fits_lds(int n_items, int cutoff);
 void spscorer_enqueue_wide_rows(mi355rec_spscorer_t h, const int *users, int n);
+// spexact.hip: what mi355rec_spscorer's two enqueues do in exact mode (h->exact) -- the rows bit for bit SciPy's, written to
+// h->scores without an atomic, then rank_rows_enqueue, or the candidates gathered from them.
+Ranking spexact_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed,
+                        bool keep_scores);
+Ranking spexact_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
+                                   const unsigned char *allowed, const CandidateRows &rows);
 // C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's
 // f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
 void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);

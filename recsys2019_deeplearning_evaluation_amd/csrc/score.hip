@@ -573,6 +573,7 @@ extern "C" int mi355rec_spscorer_create(mi355rec_spscorer_t *out, int32_t n_user
 // The score + rank half of mi355rec_spscorer_recommend (see mi355rec_scorer::enqueue).  The score rows are kept only where somebody
 // reads them: the caller, or the wide ranking.
 Ranking mi355rec_spscorer::enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) {
+    if (exact) return spexact_enqueue(this, users, n, cutoff, remove_seen, allowed, keep_scores);
     hipStream_t s = stream;
     const bool in_lds = fits_lds_rank(n_items, cutoff);
     const size_t cells = (size_t)n * n_items;

@@ -214,17 +214,32 @@ class GpuScoringMixin(_ScoringMixin):
 
 class MI355XSparseScorer(_Scorer):
     """scores[u] = A[u, :] . B for sparse A, B (ItemKNN / SLIM: A = URM_train, B = W_sparse; UserKNN: A = W_sparse,
-    B = URM_train), filtered and ranked on the device like MI355XScorer."""
+    B = URM_train), filtered and ranked on the device like MI355XScorer.
+
+    By default the products of a score are summed by LDS float atomics, in an order that can differ between two calls.  With
+    `exact=True` every score is bit for bit what SciPy's `A[users] @ B` gives for float32 operands: the stored cells of a row of A are
+    walked in their storage order (A is used as `sps.csr_matrix(A)` holds it, never sorted), product rounded before the add; calls
+    repeat bit for bit however a batch is cut into blocks.  B is uploaded with sorted indices (the order inside a row of B changes no
+    score); a B that stores a column twice in one row is refused with ValueError."""
     _PREFIX = "mi355rec_spscorer"
     EVAL_ADD = "add_spscorer"
 
-    def __init__(self, A, B, URM_seen):
+    def __init__(self, A, B, URM_seen, exact=False):
         A, B, seen = A.tocsr(), B.tocsr(), URM_seen.tocsr()
         assert A.shape[1] == B.shape[0] and seen.shape == (A.shape[0], B.shape[1])
         self.n_users, self.n_items = A.shape[0], B.shape[1]
+        self.exact = bool(exact)
+        if self.exact and not B.has_sorted_indices:
+            B = B.sorted_indices()      # (a copy: the caller's matrix stays as it is)
         arrs = [N.as_i32(A.indptr), N.as_i32(A.indices), N.as_f32(A.data), N.as_i32(B.indptr), N.as_i32(B.indices),
                 N.as_f32(B.data), N.as_i32(seen.indptr), N.as_i32(seen.indices)]
         self._create(A.shape[0], A.shape[1], B.shape[1], *[N.ptr(a) for a in arrs])
+        if self.exact:
+            try:
+                self._call("set_exact", 1)
+            except ValueError:
+                self.close()
+                raise
 
 
 class MI355XDenseScorer(_Scorer):
@@ -273,8 +288,15 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
 
     An item-based model whose W_sparse is a dense ndarray is served by MI355XDenseScorer when the class (or the object) sets
     `dense_scoring = "device"`; with the default "host" it is scored by the base class on the host, as before.  The dense scorer has a
-    cache slot of its own: other weights of the same shape are an update."""
+    cache slot of its own: other weights of the same shape are an update.
+
+    `sparse_scoring` (class or object attribute) chooses the sparse scorer's mode: "atomic", the default, sums a score's products
+    with LDS float atomics -- near-tied scores can change places between two calls; "exact" gives SciPy's float32 scores bit for
+    bit and lists by the tie rule alone (MI355XSparseScorer(exact=True)), at the price DESIGN section 17 measures.  The mode is part
+    of the cached scorer's layout: changing it builds a new scorer on the next call."""
     _SCORER_USER_BASED = False
+    SPARSE_SCORING_MODES = ("atomic", "exact")
+    sparse_scoring = "atomic"
     _sp_scorer = None
     _sp_scorer_src = None
     dense_scoring = "host"
@@ -311,11 +333,20 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
         # (SLIM's get_S_incremental_and_set_W assigns W_sparse twice per validation: the address of the first, freed matrix can be
         # handed to its successor, so an id() key would score with stale weights)
         W = self.W_sparse
+        exact = self._sparse_scoring_exact()
         A, B = (W, self.URM_train) if self._SCORER_USER_BASED else (self.URM_train, W)
         prints = (W.shape, W.nnz, _fingerprint(W.data), _fingerprint(W.indices)) if hasattr(W, "nnz") else _fingerprint(W)
-        return self._cached_scorer(self._SCORER_ATTRS[0], {"W": W}, prints, build=lambda: MI355XSparseScorer(A, B, self.URM_train))
+        return self._cached_scorer(self._SCORER_ATTRS[0], {"W": W}, prints, build=lambda: MI355XSparseScorer(A, B, self.URM_train, exact=exact),
+                                   new_layout=lambda scorer: bool(getattr(scorer, "exact", False)) != exact)
+
+    def _sparse_scoring_exact(self):
+        if self.sparse_scoring not in self.SPARSE_SCORING_MODES:
+            raise ValueError("{}: sparse_scoring must be one of {}, got {!r}".format(type(self).__name__, self.SPARSE_SCORING_MODES,
+                                                                                   self.sparse_scoring))
+        return self.sparse_scoring == "exact"
 
     def device_scorer(self):
+        self._sparse_scoring_exact()        # (an unknown mode is refused before the device is touched, whichever scorer serves)
         if self.dense_device_scorable():
             return self._get_dense_scorer()
         return self._get_sparse_scorer() if self.device_scorable() else None
