@@ -349,6 +349,17 @@ def as_f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def both_layouts(matrix):
+    """(X, arrays): X is `matrix` as float32 CSR with sorted indices; arrays are its indptr, indices and data followed by those of its
+    sorted CSC, six contiguous arrays as the create calls of the handles that keep both layouts take them."""
+    import scipy.sparse as sps
+    X = sps.csr_matrix(matrix, dtype=np.float32)
+    X.sort_indices()
+    Xc = sps.csc_matrix(X)
+    Xc.sort_indices()
+    return X, (as_i32(X.indptr), as_i32(X.indices), as_f32(X.data), as_i32(Xc.indptr), as_i32(Xc.indices), as_f32(Xc.data))
+
+
 def lds_atomic_rate():
     """ds_add_u32 lane-adds per second of the whole device on uniformly random LDS cells (the similarity build's roofline peak)."""
     rate = C.c_double(0.0)

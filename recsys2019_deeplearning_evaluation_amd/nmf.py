@@ -14,9 +14,9 @@ import ctypes as C
 import time
 
 import numpy as np
-import scipy.sparse as sps
 
 from . import _native as N
+from .block_steps import BlockPairSteps
 from .pure_svd import check_random_state, randomized_svd_device
 from .recommender_base import BaseMatrixFactorizationRecommender, check_matrix
 from .scoring import GpuScoringMixin
@@ -35,39 +35,11 @@ def check_permutation(permutation, k):
     return N.as_i32(p)
 
 
-class NMF_MI355X_Steps(N.Handle):
+class NMF_MI355X_Steps(BlockPairSteps):
     """The URM in both layouts and the two float32 blocks on the device: side 0 is W (n_users, k), side 1 is Ht = H^T (n_items, k)."""
     _PREFIX = "mi355rec_nmf"
-
-    def __init__(self, URM_train, k):
-        X = sps.csr_matrix(URM_train, dtype=np.float32)
-        X.sort_indices()
-        Xc = sps.csc_matrix(X)
-        Xc.sort_indices()
-        self.n_users, self.n_items = X.shape
-        self.k = int(k)
-        self.nnz = int(X.nnz)
-        arrays = (N.as_i32(X.indptr), N.as_i32(X.indices), N.as_f32(X.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
-        self._create(self.n_users, self.n_items, self.k, *[N.ptr(a) for a in arrays])
-
-    def rows_of(self, side):
-        return self.n_items if side else self.n_users
-
-    def _side(self, side):
-        if side not in (0, 1):
-            raise ValueError("side %r: 0 (W, users) or 1 (Ht, items)" % (side,))
-        return int(side)
-
-    def set_block(self, side, X):
-        X = N.as_f32(X)
-        if X.shape != (self.rows_of(self._side(side)), self.k):
-            raise ValueError("block of side %r must be %d x %d, got %r" % (side, self.rows_of(side), self.k, X.shape))
-        self._call("set_block", side, N.ptr(X))
-
-    def get_block(self, side):
-        X = np.empty((self.rows_of(self._side(side)), self.k), np.float32)
-        self._call("get_block", side, N.ptr(X))
-        return X
+    _SIDE_NAMES = ("W, users", "Ht, items")
+    k = property(lambda self: self.width)
 
     def fill_block(self, side, value):
         self._call("fill_block", self._side(side), C.c_float(value))
@@ -100,13 +72,8 @@ class NMF_MI355X_Steps(N.Handle):
 
     def fit_info(self):
         ms = (C.c_double * len(PHASES))()
-        v = [C.c_int64() for _ in range(5)]
-        ones = C.c_int32()
-        self._call("fit_info", ms, *[C.byref(x) for x in v], C.byref(ones))
-        info = {name: ms[n] for n, name in enumerate(PHASES)}
-        info.update(launches=v[0].value, calls=v[1].value, create_bytes=v[2].value, h2d_bytes=v[3].value, d2h_bytes=v[4].value,
-                    all_ones=bool(ones.value))
-        return info
+        tail = self._fit_info_tail(ms)
+        return dict({name: ms[n] for n, name in enumerate(PHASES)}, **tail)
 
 
 def _nndsvda(A, k, random_seed, stats):

@@ -19,6 +19,7 @@ import scipy.linalg as sla
 import scipy.sparse as sps
 
 from . import _native as N
+from .block_steps import BlockPairSteps
 from .recommender_base import BaseItemSimilarityMatrixRecommender, BaseMatrixFactorizationRecommender, check_matrix
 from .scoring import GpuScoringMixin, GpuSimilarityScoringMixin, MI355XScorer
 
@@ -43,36 +44,11 @@ def check_random_state(seed):
     raise ValueError("%r cannot be used to seed a numpy.random.RandomState instance" % seed)
 
 
-class PureSVD_MI355X_Steps(N.Handle):
+class PureSVD_MI355X_Steps(BlockPairSteps):
     """The URM in both layouts and two float32 blocks on the device: side 0 is (n_users, r), side 1 is (n_items, r)."""
     _PREFIX = "mi355rec_svd"
-
-    def __init__(self, URM_train, r):
-        X = sps.csr_matrix(URM_train, dtype=np.float32)
-        X.sort_indices()
-        Xc = sps.csc_matrix(X)
-        Xc.sort_indices()
-        self.n_users, self.n_items = X.shape
-        self.r = int(r)
-        self.nnz = int(X.nnz)
-        arrays = (N.as_i32(X.indptr), N.as_i32(X.indices), N.as_f32(X.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
-        self._create(self.n_users, self.n_items, self.r, *[N.ptr(a) for a in arrays])
-
-    def rows_of(self, side):
-        return self.n_items if side else self.n_users
-
-    def set_block(self, side, X):
-        X = N.as_f32(X)
-        if side not in (0, 1) or X.shape != (self.rows_of(side), self.r):
-            raise ValueError("block of side %r must be %d x %d, got %r" % (side, self.rows_of(side) if side in (0, 1) else -1, self.r, X.shape))
-        self._call("set_block", side, N.ptr(X))
-
-    def get_block(self, side):
-        if side not in (0, 1):
-            raise ValueError("side %r: 0 (users) or 1 (items)" % (side,))
-        X = np.empty((self.rows_of(side), self.r), np.float32)
-        self._call("get_block", side, N.ptr(X))
-        return X
+    _SIDE_NAMES = ("users", "items")
+    r = property(lambda self: self.width)
 
     def product(self, dst_side):
         """dst_side 0: block[0] = URM . block[1]; dst_side 1: block[1] = URM^T . block[0]."""
@@ -91,11 +67,8 @@ class PureSVD_MI355X_Steps(N.Handle):
 
     def fit_info(self):
         ms = [C.c_double() for _ in range(3)]
-        v = [C.c_int64() for _ in range(5)]
-        ones = C.c_int32()
-        self._call("fit_info", *[C.byref(x) for x in ms + v], C.byref(ones))
-        return {"product_ms": ms[0].value, "gram_ms": ms[1].value, "apply_ms": ms[2].value, "launches": v[0].value, "calls": v[1].value,
-                "create_bytes": v[2].value, "h2d_bytes": v[3].value, "d2h_bytes": v[4].value, "all_ones": bool(ones.value)}
+        tail = self._fit_info_tail(*[C.byref(x) for x in ms])
+        return dict({"product_ms": ms[0].value, "gram_ms": ms[1].value, "apply_ms": ms[2].value}, **tail)
 
 
 def _inverse_cholesky_factor(G):

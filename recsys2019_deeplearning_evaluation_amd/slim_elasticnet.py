@@ -41,12 +41,8 @@ class SLIMElasticNet_MI355X_Fit(N.Handle):
     _PREFIX = "mi355rec_slimen"
 
     def __init__(self, URM_train):
-        X = sps.csr_matrix(URM_train, dtype=np.float32)
-        X.sort_indices()
-        Xc = sps.csc_matrix(X)
-        Xc.sort_indices()
+        X, arrays = N.both_layouts(URM_train)
         self.n_users, self.n_items = X.shape
-        arrays = (N.as_i32(X.indptr), N.as_i32(X.indices), N.as_f32(X.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
         self._create(self.n_users, self.n_items, *[N.ptr(a) for a in arrays])
 
     def fit_range(self, start, end, seeds, alpha, l1_ratio, positive_only, topK, max_iter=100, tol=1e-4):

@@ -127,3 +127,44 @@ def csr_columns_as_slabs(W, topK):
         o = np.argsort(-W.data[s:e], kind="stable")
         idx[c, :e - s] = W.indices[s:e][o]; val[c, :e - s] = W.data[s:e][o]
     return idx, val
+
+
+def block_pair_create_refusals(prefix, width_noun, nmf=False):
+    """Every refusal of mi355rec_<prefix>_create (the PureSVD and NMF handles share them), word for word.  All of them come before the
+    device is touched.  Returns the messages seen, in the order of the checks."""
+    import ctypes as C
+    from recsys2019_deeplearning_evaluation_amd import _native as N
+    lib = N.load()
+    create = getattr(lib, "mi355rec_%s_create" % prefix)
+    # 3 users x 4 items: [[1, 0, 0, 2], [0, 0, 0, 0], [0, 3, 0, 0]]
+    good = dict(n_users=3, n_items=4, width=2, row_ptr=[0, 2, 2, 3], row_idx=[0, 3, 1], row_val=[1, 2, 3], col_ptr=[0, 1, 2, 2, 3], col_idx=[0, 2, 0],
+                col_val=[1, 3, 2])
+    big = 128 * 65535 + 1
+
+    def refused(out=True, **changes):
+        a = dict(good, **changes)
+        arrays = [None if a[name] is None else (N.as_f32 if name.endswith("val") else N.as_i32)(a[name])
+                  for name in ("row_ptr", "row_idx", "row_val", "col_ptr", "col_idx", "col_val")]
+        h = C.c_void_p()
+        rc = create(C.byref(h) if out else None, a["n_users"], a["n_items"], a["width"], *[N.ptr(x) for x in arrays])
+        assert rc == N.E_INVALID and not h.value, changes
+        return lib.mi355rec_last_error().decode()
+
+    seen = [refused(out=False), refused(row_ptr=None), refused(col_ptr=None), refused(row_val=None), refused(col_idx=None)]
+    assert seen == ["NULL argument"] * 5
+    seen += [refused(n_users=0), refused(n_items=-1)]
+    assert seen[-2:] == ["empty URM (0 x 4)", "empty URM (3 x -1)"]
+    seen += [refused(width=w) for w in (0, -3, 4097)]
+    assert seen[-3:] == ["%s = %d outside [1, 4096]" % (width_noun, w) for w in (0, -3, 4097)]
+    seen.append(refused(col_ptr=[0, 1, 2, 2, 2]))
+    assert seen[-1] == "the two layouts hold 3 and 2 cells"
+    seen.append(refused(n_users=big, row_ptr=np.zeros(big + 1, np.int32), col_ptr=[0, 0, 0, 0, 0], row_idx=None, col_idx=None, row_val=None, col_val=None))
+    assert seen[-1] == "more than 8 M rows on a side"
+    seen += [refused(row_ptr=[1, 2, 2, 3]), refused(row_ptr=[0, 2, 1, 3]), refused(col_ptr=[0, 1, 2, 4, 3]), refused(row_idx=[0, 4, 1]),
+             refused(col_idx=[0, 2, -1]), refused(col_idx=[3, 2, 0])]
+    assert seen[-6:] == ["row pointers do not start at 0", "row pointers decrease at 1", "row pointers decrease at 3", "index 4 outside [0, 4)",
+                         "index -1 outside [0, 3)", "index 3 outside [0, 3)"]
+    if nmf:
+        seen += [refused(row_val=[1, -1, 3]), refused(row_val=[1, 2, -0.25], col_val=[1, -0.25, 2])]
+        assert seen[-2:] == ["negative value -1 in the URM", "negative value -0.25 in the URM"]
+    return seen

@@ -174,6 +174,9 @@ def test_bad_abi_arguments_are_refused_before_touching_the_device():
     bad.indices[0] = 10                       # a column outside the matrix
     with pytest.raises(ValueError):
         NMF_MI355X_Steps(bad, 4)
+    # every refusal of create, word for word: the ones both handle types share, the width with NMF's noun, the negative value
+    from _util import block_pair_create_refusals
+    assert len(block_pair_create_refusals("nmf", "number of components k", nmf=True)) == 20
     # side and loss are looked at before the handle is: a wrong one is reported as such even on a NULL handle
     lib = N.load()
     perm = N.as_i32(np.arange(4))

@@ -136,6 +136,9 @@ def test_bad_arguments_raise_value_error_before_touching_the_device():
         Xc = sps.csc_matrix(X)
         arrays = (N.as_i32(bad.indptr), N.as_i32(bad.indices), N.as_f32(bad.data), N.as_i32(Xc.indptr), N.as_i32(Xc.indices), N.as_f32(Xc.data))
         N.check(N.load().mi355rec_svd_create(C.byref(h), 20, 10, 4, *[N.ptr(a) for a in arrays]))
+    # every refusal of create, word for word: the ones both handle types share and the width with PureSVD's noun
+    from _util import block_pair_create_refusals
+    assert len(block_pair_create_refusals("svd", "block width r")) == 18
 
 
 def test_no_cpu_fallback_without_device():
@@ -150,6 +153,6 @@ def test_no_cpu_fallback_without_device():
 
 
 def test_source_of_the_kernels_names_nothing_per_width():
-    """One product kernel for every block width: the template parameters of svd.hip are the all-ones switch only."""
-    text = open(os.path.join(ROOT, "recsys2019_deeplearning_evaluation_amd", "csrc", "svd.hip")).read()
+    """One product kernel for every block width: the template parameters of its kernel-only header are the all-ones switch only."""
+    text = open(os.path.join(ROOT, "recsys2019_deeplearning_evaluation_amd", "csrc", "blocks_kernels.cuh")).read()
     assert re.findall(r"template <([^>]*)>", text) == ["bool ONES"]
