@@ -20,6 +20,26 @@ __device__ __forceinline__ Chunk<T, VEC> load_chunk(const T *row, int chunk, boo
     return r;
 }
 
+// How a row chunk (next row version, optimiser moments) leaves the wavefront.  A plain store stays dirty in the L2 of the wavefront's
+// XCD until the release at the end of the kernel writes every such line back, on the chain between two mini-batches; a write-through
+// (sc1, agent scope) store goes on to memory while the slower wavefronts of the launch still run.  No wait and no fence go with
+// it: the kernel boundary stays the synchronisation, only the time at which the bytes leave L2 changes.
+// (The compiler does not see the instruction inside the statement: `s_nop 1` keeps its next instruction from overwriting the four
+// data registers before the store has read them.  Nothing waits for the store; the wavefront only ends after it.)
+enum RowStore { ROW_STORE_PLAIN = 0, ROW_STORE_THROUGH = 1 };
+template <int STORE, class T, int VEC>
+__device__ __forceinline__ void store_chunk(T *at, const Chunk<T, VEC> &c) {
+    static_assert(sizeof(Chunk<T, VEC>) == 16, "a row chunk is one 16-byte store");
+    if constexpr (STORE == ROW_STORE_THROUGH) {
+        typedef unsigned word4 __attribute__((ext_vector_type(4)));
+        word4 bits;
+        __builtin_memcpy(&bits, &c, sizeof bits);
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(at), "v"(bits) : "memory");
+    } else {
+        *reinterpret_cast<Chunk<T, VEC> *>(at) = c;
+    }
+}
+
 // Adam's 1 - beta^t for the 1-based mini-batch index t
 template <class T, class P> __device__ __forceinline__ void adam_powers(const P &p, long long t, T &pw1, T &pw2) {
     pw1 = (T)1;
@@ -103,8 +123,8 @@ __device__ __forceinline__ Rows<T, VEC, KI, BPR> load_rows(const MfParams<T> &p,
 // `hdr` / `slot` = the mini-batch's headers and pair records by slot, `wv` = this wavefront's header slot, `tpb` = header slots per
 // mini-batch, `stamps` = p.ticks != NULL: what the header's address is made of.  The one-model kernel gets them as leading
 // kernel arguments, which gfx950 preloads into scalar registers (ARGS_HERE: the request for the other arguments goes out behind the
-// header's, not in front of it), the group kernel from its table row.
-template <int ALGO, class T, int VEC, int LPR, int KI, bool ARGS_HERE>
+// header's, not in front of it), the group kernel from its table row.  STORE: the RowStore of every row chunk the body writes.
+template <int ALGO, class T, int VEC, int LPR, int KI, bool ARGS_HERE, int STORE>
 __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int batch_local, const int wg, const int wv, const int tpb,
                                               const TaskHeader *hdr, const int4 *slot, const bool stamps) {
     constexpr int G = 64 / LPR;
@@ -330,9 +350,9 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
                     const T step = adapt_cell(p, gm, m1.v[e], m2.v[e], pw1, pw2);
                     out.v[e] = moved(own[c].v[e], p.lr, step);
                 }
-                *reinterpret_cast<Ch *>(Wn + at) = out;
-                if (p.sgd_mode != MI355REC_SGD) *reinterpret_cast<Ch *>(c1 + at) = m1;
-                if (p.sgd_mode == MI355REC_ADAM) *reinterpret_cast<Ch *>(c2 + at) = m2;
+                store_chunk<STORE>(Wn + at, out);
+                if (p.sgd_mode != MI355REC_SGD) store_chunk<STORE>(c1 + at, m1);
+                if (p.sgd_mode == MI355REC_ADAM) store_chunk<STORE>(c2 + at, m2);
             }
             if (bias && li == 0) {
                 T *bn = is_item ? (own_buf ? p.bi0 : p.bi1) : (own_buf ? p.bu0 : p.bu1);
@@ -372,9 +392,9 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
                         const T step = adapt_cell(p, gm, m1.v[v], m2.v[v], pw1, pw2);
                         out.v[v] = moved(e == 1 ? b : cc, p.lr, step);
                     }
-                    *reinterpret_cast<Ch *>(Wn + at) = out;
-                    if (p.sgd_mode != MI355REC_SGD) *reinterpret_cast<Ch *>(c1 + at) = m1;
-                    if (p.sgd_mode == MI355REC_ADAM) *reinterpret_cast<Ch *>(c2 + at) = m2;
+                    store_chunk<STORE>(Wn + at, out);
+                    if (p.sgd_mode != MI355REC_SGD) store_chunk<STORE>(c1 + at, m1);
+                    if (p.sgd_mode == MI355REC_ADAM) store_chunk<STORE>(c2 + at, m2);
                 }
             }
         }
@@ -413,7 +433,10 @@ __global__ __launch_bounds__(256) void mf_batch_kernel(const TaskHeader *hdr, co
     // (Measured and rejected, round 4: a launch over a third of the slots with a loop over the slots in use, as the group launch does --
     // BPR 198 against 196 M samples/s, FunkSVD, whose slots are nearly all in use, 102 against 161 M.)
     const int wv = __builtin_amdgcn_readfirstlane((blockIdx.x * wg_stride + wg_base) * 4 + (threadIdx.x >> 6));
-    mf_batch_body<ALGO, T, VEC, LPR, KI, true>(p, batch_local, blockIdx.x, wv, tasks_per_batch, hdr, slot, stamps != 0);
+    // (Write-through row stores where they were measured to win: BPR under plain sgd, float32 and float64, + 6 % and + 5 % per epoch.
+    // BPR with optimiser moments, - 2 %, FunkSVD, - 7 %, and the replica-batched launch below, - 2 %, keep plain stores.)
+    constexpr int STORE = PLAIN_SGD && ALGO == MI355REC_MF_BPR ? ROW_STORE_THROUGH : ROW_STORE_PLAIN;
+    mf_batch_body<ALGO, T, VEC, LPR, KI, true, STORE>(p, batch_local, blockIdx.x, wv, tasks_per_batch, hdr, slot, stamps != 0);
 }
 
 // REPLICA-BATCHED launch: mini-batch `batch_local` of R independent models in one grid (blockIdx.y = model).  A single model's
@@ -454,7 +477,7 @@ __global__ __launch_bounds__(256, (PLAIN_SGD && ALGO == MI355REC_MF_BPR && sizeo
     const int4 *slot = p.slot_recs + (size_t)batch_local * p.slot_rec_stride;
     for (int wg = blockIdx.x; wg * 4 < used; wg += gridDim.x) {
         const int wv = __builtin_amdgcn_readfirstlane((wg * p.wg_stride + p.wg_base) * 4 + (threadIdx.x >> 6));
-        mf_batch_body<ALGO, T, VEC, LPR, KI, false>(p, batch_local, wg, wv, p.tasks_per_batch, hdr, slot, p.ticks != nullptr);
+        mf_batch_body<ALGO, T, VEC, LPR, KI, false, ROW_STORE_PLAIN>(p, batch_local, wg, wv, p.tasks_per_batch, hdr, slot, p.ticks != nullptr);
     }
 }
 // Sampler and schedule of every member in ONE launch each (model on the last grid dimension): as 4 x R small launches on R
