@@ -96,7 +96,9 @@ struct mi355rec_mf : Handle {
     // the in-LDS schedule
     struct LdsSchedule {
         bool fast_schedule = false;              // available to this handle (cached: see MfShape::fast_schedule)
-        DeviceBuffer<unsigned> touched;          // (row, mini-batch) bitmap
+        bool bit_rows = false, bit_rows_decided = false;      // bit rows in place of the bitmap (cached like fast_schedule, decided once)
+        DeviceBuffer<unsigned> touched;          // (row, mini-batch) bitmap: only without bit rows
+        DeviceBuffer<unsigned> bit_rows_buf;     // [mini-batches of one schedule][row words]
         DeviceBuffer<int> sorted_slot, qtask, used;
         DeviceBuffer<unsigned long long> ticks;  // MI355REC_MF_TICKS: the sort kernel's phase stamps
     } lds;
@@ -133,6 +135,7 @@ MfShape shape_of(const mi355rec_mf *h) {
     s.batch_size = h->cfg.batch_size;
     s.sharded = h->shard.rank >= 0;
     s.fast_schedule = h->lds.fast_schedule;
+    s.bit_rows = h->lds.bit_rows;
     return s;
 }
 
@@ -265,19 +268,43 @@ void launch_sampler(mi355rec_mf *h, const MfParams<T> &p, hipStream_t on = nullp
 
 // ---- schedules ------------------------------------------------------------------------------------------------------------------
 size_t sched_lds(int np) { return sched_lds_bytes(np, sched_sort_storage_bytes(np)); }
+// ... of a launch: with the mini-batch's bit row behind the flags
+size_t sched_lds(const FastSchedParams &f) { return sched_lds(f.np) + (f.bit_rows ? sizeof(unsigned) * (size_t)f.row_words : 0); }
 
+// what bit_rows_fit() needs of the current device: the LDS a workgroup may have, and what the sort kernels declare statically
+// (the block scan's scratch; the one-model and the group kernel share the body)
+struct SchedLdsLimits {
+    size_t limit, static_bytes;
+};
+SchedLdsLimits sched_lds_limits() {
+    static SchedLdsLimits cached[64] = {};
+    int dev = 0, limit = 0;
+    MI_HIP(hipGetDevice(&dev));
+    if (dev >= 0 && dev < 64 && cached[dev].limit) return cached[dev];
+    MI_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    hipFuncAttributes one{}, group{};
+    MI_HIP(hipFuncGetAttributes(&one, reinterpret_cast<const void *>(mf_sched_sort_kernel)));
+    MI_HIP(hipFuncGetAttributes(&group, reinterpret_cast<const void *>(mf_group_sched_sort_kernel)));
+    const SchedLdsLimits l{(size_t)std::max(limit, 0), std::max(one.sharedSizeBytes, group.sharedSizeBytes)};
+    if (dev >= 0 && dev < 64) cached[dev] = l;
+    return l;
+}
+
+// (everything a workgroup may have: the largest mini-batch without a bit row, and every bit row bit_rows_fit() lets through)
 void set_sched_sort_attribute(const void *kernel, bool (&attr_set)[64]) {
     int dev = 0;
     MI_HIP(hipGetDevice(&dev));                 // the attribute is per DEVICE, not per process
     if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        MI_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sched_lds(FAST_MAX_SLOTS)));
+        const SchedLdsLimits l = sched_lds_limits();
+        const size_t bytes = std::max(sched_lds(FAST_MAX_SLOTS), l.limit > l.static_bytes ? l.limit - l.static_bytes : 0);
+        MI_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
 }
 
 FastSchedParams fast_sched_params(mi355rec_mf *h, const MfKnobs &knobs, long long n_samples) {
     const MfShape s = shape_of(h);
-    const FastSchedNumbers n = fast_sched_numbers(s, knobs, sched_sort_storage_bytes(sched_np(tasks_per_batch(s))));
+    const FastSchedNumbers n = fast_sched_numbers_bit_rows(s, knobs, sched_sort_storage_bytes(sched_np(tasks_per_batch(s))));
     FastSchedParams f;
     memset(&f, 0, sizeof(f));                   // (padding bytes included: the group compares tables bytewise)
     f.n_samples = n_samples;
@@ -290,6 +317,8 @@ FastSchedParams fast_sched_params(mi355rec_mf *h, const MfKnobs &knobs, long lon
     f.words = n.words; f.group = n.group; f.fuse = n.fuse; f.fill_all = n.fill_all;
     f.su = h->buf.su.ptr; f.si = h->buf.si.ptr; f.sj = h->buf.sj.ptr; f.sr = h->buf.sr.ptr;
     f.touched = h->lds.touched.ptr; f.par = h->par.ptr;
+    f.row_words = n.row_words;
+    f.bit_rows = n.bit_rows ? h->lds.bit_rows_buf.ptr : nullptr;
     f.sorted_slot = h->lds.sorted_slot.ptr; f.qtask = h->lds.qtask.ptr; f.used = h->lds.used.ptr;
     f.tasks = h->buf.tasks.ptr; f.recs = h->buf.recs.ptr; f.slot_recs = h->buf.slot_recs.ptr;
     f.ticks = h->lds.ticks.ptr;
@@ -316,9 +345,10 @@ void enqueue_fast_schedule(mi355rec_mf *h, const FastSchedParams &f, long long n
     hipStream_t s = h->stream;
     static bool attr_set[64] = {};
     set_sched_sort_attribute(reinterpret_cast<const void *>(mf_sched_sort_kernel), attr_set);
-    hipLaunchKernelGGL(mf_sched_sort_kernel, dim3((unsigned)n_batches), dim3(SCHED_THREADS), sched_lds(f.np), s, f);
+    hipLaunchKernelGGL(mf_sched_sort_kernel, dim3((unsigned)n_batches), dim3(SCHED_THREADS), sched_lds(f), s, f);
+    if (f.bit_rows) hipLaunchKernelGGL(mf_sched_parity_kernel, dim3(div_up(f.row_words, 64)), dim3(PARITY_THREADS), 0, s, f, (int)n_batches);
     hipLaunchKernelGGL(mf_sched_emit_kernel, dim3(div_up(f.batch_size, 256), (unsigned)n_batches), dim3(256), 0, s, f);
-    hipLaunchKernelGGL(mf_sched_finish_kernel, dim3(div_up(f.n_entries, 256)), dim3(256), 0, s, f);
+    if (!f.bit_rows) hipLaunchKernelGGL(mf_sched_finish_kernel, dim3(div_up(f.n_entries, 256)), dim3(256), 0, s, f);
 }
 
 SchedParams radix_sched_params(mi355rec_mf *h, const GeneralSched &g, long long n_samples) {
@@ -477,14 +507,24 @@ void alloc_task_tables(mi355rec_mf *h, const BufferPlan &b) {
         h->lds.sorted_slot.alloc(b.sorted_slot);
         h->lds.qtask.alloc(b.qtask);
         h->lds.used.alloc(b.used);
-        if (!h->lds.touched.ptr) h->lds.touched.alloc_zero(b.touched, h->stream);
+        if (b.touched && !h->lds.touched.ptr) h->lds.touched.alloc_zero(b.touched, h->stream);
+        if (h->lds.bit_rows_buf.count < b.bit_rows) h->lds.bit_rows_buf.alloc(b.bit_rows);      // (every row a stream reads, it has written)
     }
     h->buf.batch_capacity = b.table_batches;
 }
 
 // `whole_stream`: the caller schedules the stream in one piece whatever its length (group members, exact multi-GPU mode)
 void ensure_stream_capacity(mi355rec_mf *h, const MfKnobs &knobs, size_t n_samples, long long n_batches, bool whole_stream = false) {
-    const BufferPlan b = buffer_plan(shape_of(h), knobs, n_samples, n_batches, whole_stream);
+    // bit rows or the per-row bitmap: decided by the handle's first call that plans buffers, for good (both leave the same par[])
+    if (!h->lds.bit_rows_decided && h->cfg.algorithm != MI355REC_MF_ASY_SVD) {
+        const MfShape s = shape_of(h);
+        if (fast_schedule_fits(s, knobs, 1)) {
+            const SchedLdsLimits l = sched_lds_limits();
+            h->lds.bit_rows = bit_rows_fit(s, knobs, sched_sort_storage_bytes(sched_np(tasks_per_batch(s))), l.static_bytes, l.limit);
+        }
+        h->lds.bit_rows_decided = true;
+    }
+    const BufferPlan b = buffer_plan_bit_rows(shape_of(h), knobs, n_samples, n_batches, whole_stream);
     if (h->buf.capacity < n_samples) {
         h->drop_graphs();       // they hold the old buffer addresses
         h->buf.su.alloc(n_samples);
@@ -924,11 +964,19 @@ void group_enqueue_schedule(mi355rec_mf_group *g, const MfParams<T> *table, cons
     hipLaunchKernelGGL(mf_group_epoch_advance_kernel<T>, dim3(div_up(R, 64)), dim3(64), 0, s, table, R);
     static bool attr_set[64] = {};
     set_sched_sort_attribute(reinterpret_cast<const void *>(mf_group_sched_sort_kernel), attr_set);
-    int max_entries = 0;
-    for (const auto &f : g->host_sched_table) max_entries = std::max(max_entries, f.n_entries);
-    hipLaunchKernelGGL(mf_group_sched_sort_kernel, dim3((unsigned)nb, R), dim3(SCHED_THREADS), sched_lds(f0.np), s, sched_table);
+    // (all members on bit rows or none: group_sched_table; the rows' lengths are the members' own)
+    int max_entries = 0, max_row_words = 0;
+    size_t lds = 0;
+    for (const auto &f : g->host_sched_table) {
+        max_entries = std::max(max_entries, f.n_entries);
+        max_row_words = std::max(max_row_words, f.row_words);
+        lds = std::max(lds, sched_lds(f));
+    }
+    const bool bit_rows = f0.bit_rows != nullptr;
+    hipLaunchKernelGGL(mf_group_sched_sort_kernel, dim3((unsigned)nb, R), dim3(SCHED_THREADS), lds, s, sched_table);
+    if (bit_rows) hipLaunchKernelGGL(mf_group_sched_parity_kernel, dim3(div_up(max_row_words, 64), R), dim3(PARITY_THREADS), 0, s, sched_table, (int)nb);
     hipLaunchKernelGGL(mf_group_sched_emit_kernel, dim3(div_up(f0.batch_size, 256), (unsigned)nb, R), dim3(256), 0, s, sched_table);
-    hipLaunchKernelGGL(mf_group_sched_finish_kernel, dim3(div_up(max_entries, 256), R), dim3(256), 0, s, sched_table);
+    if (!bit_rows) hipLaunchKernelGGL(mf_group_sched_finish_kernel, dim3(div_up(max_entries, 256), R), dim3(256), 0, s, sched_table);
 }
 
 // the shared chain of mini-batch launches of one epoch, on the group's stream
@@ -999,6 +1047,9 @@ std::vector<FastSchedParams> group_sched_table(mi355rec_mf_group *g, const MfKno
     for (size_t m = 0; m < g->members.size(); ++m) {
         mi355rec_mf *h = g->members[m];
         all_fast = all_fast && runs_fast_schedule(shape_of(h), knobs, nb);
+        // one launch runs either the parity kernel in front of the emit kernel or the finish kernel behind it: members that disagree
+        // about bit rows (one too large for LDS, or created under MI355REC_MF_ROW_BITMAP) schedule on their own streams, as a whole
+        all_fast = all_fast && h->lds.bit_rows == g->members[0]->lds.bit_rows;
         if (!all_fast) continue;
         sched[m] = fast_sched_params(h, knobs, nb * (long long)h->cfg.batch_size);
         // (the group's mini-batch kernel reads `used` and never looks at a slot past the last workgroup in use: two thirds of the

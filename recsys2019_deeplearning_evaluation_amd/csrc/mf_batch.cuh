@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256, (PLAIN_SGD && ALGO == MI355REC_MF_BPR && sizeo
 // streams they took a third of a 32-model epoch.
 __device__ __forceinline__ void globalize(FastSchedParams &f) {
     f.su = as_global(f.su); f.si = as_global(f.si); f.sj = as_global(f.sj); f.sr = as_global(f.sr);
-    f.touched = as_global(f.touched); f.par = as_global(f.par); f.sorted_slot = as_global(f.sorted_slot); f.qtask = as_global(f.qtask);
+    f.touched = as_global(f.touched); f.bit_rows = as_global(f.bit_rows); f.par = as_global(f.par); f.sorted_slot = as_global(f.sorted_slot); f.qtask = as_global(f.qtask);
     f.used = as_global(f.used); f.tasks = as_global(f.tasks); f.recs = as_global(f.recs); f.slot_recs = as_global(f.slot_recs);
 }
 template <int ALGO, class T>
@@ -506,7 +506,12 @@ __global__ __launch_bounds__(SCHED_THREADS) void mf_group_sched_sort_kernel(cons
 __global__ __launch_bounds__(256) void mf_group_sched_emit_kernel(const FastSchedParams *__restrict__ table) {
     FastSchedParams f = table[blockIdx.z];
     globalize(f);
-    mf_sched_emit_body(f);
+    mf_sched_emit_either(f);
+}
+__global__ __launch_bounds__(PARITY_THREADS) void mf_group_sched_parity_kernel(const FastSchedParams *__restrict__ table, const int n_batches) {
+    FastSchedParams f = table[blockIdx.y];
+    globalize(f);
+    mf_sched_parity_body(f, n_batches);
 }
 __global__ __launch_bounds__(256) void mf_group_sched_finish_kernel(const FastSchedParams *__restrict__ table) {
     FastSchedParams f = table[blockIdx.y];

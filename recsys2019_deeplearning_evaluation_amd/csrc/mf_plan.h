@@ -48,6 +48,7 @@ struct MfKnobs {
     bool group_per_member_schedule = false;   // GROUP_PER_MEMBER_SCHEDULE: a group's members sample and schedule on their own streams
     bool group_no_lookahead = false;          // GROUP_NO_LOOKAHEAD: the group's next schedule does not run beside the mini-batches
     bool no_graph = false;                    // MI355REC_NO_GRAPH: plain launches only (rocprofv3 on ROCm 7.2 crashes while tracing graph replays)
+    bool row_bitmap = false;                  // ROW_BITMAP: the in-LDS schedule keeps the per-row bitmap built by global atomics (no bit rows)
 };
 
 // the only place of mf.hip and its headers that reads the environment
@@ -61,6 +62,7 @@ inline MfKnobs read_mf_knobs() {
     k.group_per_member_schedule = is_set("MI355REC_MF_GROUP_PER_MEMBER_SCHEDULE");
     k.group_no_lookahead = is_set("MI355REC_MF_GROUP_NO_LOOKAHEAD");
     k.no_graph = is_set("MI355REC_NO_GRAPH");
+    k.row_bitmap = is_set("MI355REC_MF_ROW_BITMAP");
     return k;
 }
 
@@ -79,6 +81,9 @@ struct MfShape {
     // while the radix-sort schedule, which fills one mini-batch of pair records at most, runs.  Nothing toggles the switch during a
     // handle's life.
     bool fast_schedule = false;
+    // The handle's CACHED decision for the bit rows of the in-LDS schedule (bit_rows_fit as the call that allocated the task tables saw
+    // it); false: the per-row bitmap `touched`, global atomics and the finish kernel.
+    bool bit_rows = false;
 };
 
 inline int bits_for(unsigned long long n_values) {   // bits needed for values 0 .. n_values - 1 (at least 1)
@@ -204,6 +209,7 @@ inline size_t sched_lds_bytes(int np, size_t sort_storage_bytes) {
 
 struct FastSchedNumbers {
     int np, slot_bits, entry_bits, mid_bytes, words, group, fuse, fill_all;
+    int row_words, bit_rows;    // words of a mini-batch's bit row; 1: the schedule runs on bit rows (both 0 from fast_sched_numbers)
 };
 inline FastSchedNumbers fast_sched_numbers(const MfShape &s, const MfKnobs &knobs, size_t sort_storage_bytes) {
     FastSchedNumbers f{};
@@ -217,6 +223,123 @@ inline FastSchedNumbers fast_sched_numbers(const MfShape &s, const MfKnobs &knob
     f.fuse = s.algorithm == MI355REC_MF_BPR && !s.sharded && !knobs.no_fuse;
     f.fill_all = 1;
     return f;
+}
+
+// ---- bit rows: which buffer holds a row's version at mini-batch b, without atomics ---------------------------------------------------
+// A workgroup of the sort kernel is one mini-batch, so bit b of every row is written by workgroup b alone: stored [mini-batch][row bit]
+// the workgroup collects its mini-batch's touch bits in LDS and writes the row out once, coalesced.  One pass down the word columns
+// (parity_load / parity_store below) turns the touch bits into version parities in place and carries par[] to the end of the
+// stream; the emit kernel then reads one word per row.  The other layout -- touched[row][FAST_MAX_BATCHES / 32], one device-scope
+// atomicOr per run, a finish kernel that scans and clears it, eight masked popcounts per row in the emit kernel -- remains for shapes
+// whose bit row does not fit LDS and under MI355REC_MF_ROW_BITMAP.
+//
+// words of one mini-batch's bit row: a multiple of 4, so that rows are 16-byte aligned and move 16 bytes at a time
+inline int bit_row_words(long long n_entries) { return (int)((ceil_div(n_entries, 32) + 3) / 4 * 4); }
+// LDS of the sort kernel with a bit row behind the once-touched flags (sched_lds_bytes is a multiple of 16)
+inline size_t sched_lds_bytes_bit_rows(int np, size_t sort_storage_bytes, long long n_entries) {
+    return sched_lds_bytes(np, sort_storage_bytes) + sizeof(unsigned) * (size_t)bit_row_words(n_entries);
+}
+// keys + middle + flags + bit row + the kernel's static LDS stay within the device's limit per workgroup
+inline bool bit_rows_fit(const MfShape &s, const MfKnobs &knobs, size_t sort_storage_bytes, size_t static_lds_bytes, size_t lds_limit) {
+    if (knobs.row_bitmap) return false;
+    const int np = sched_np(tasks_per_batch(s));
+    return sched_lds_bytes_bit_rows(np, sort_storage_bytes, (long long)s.n_users + s.n_items) + static_lds_bytes <= lds_limit;
+}
+// fast_sched_numbers with the handle's cached decision (MfShape::bit_rows)
+inline FastSchedNumbers fast_sched_numbers_bit_rows(const MfShape &s, const MfKnobs &knobs, size_t sort_storage_bytes) {
+    FastSchedNumbers f = fast_sched_numbers(s, knobs, sort_storage_bytes);
+    f.row_words = bit_row_words((long long)s.n_users + s.n_items);
+    f.bit_rows = s.bit_rows ? 1 : 0;
+    return f;
+}
+
+// The column pass.  Word column w of the bit rows holds rows 32 w .. 32 w + 31; down the column, the word of mini-batch b is
+// replaced by `running` (the buffer of each row's version in front of b) and `running ^= touch word`.  The mini-batches of a stream
+// are cut into PARITY_PARTS consecutive parts of parity_part_len() each: a part's loads are independent of one another, its XOR is
+// all the later parts need of it.  The kernel gives a part to a wavefront (a lane per column, the XORs meet in LDS); parity_column()
+// walks the parts in turn -- the same functions, which is what tests/test_mf_bit_rows_plan.py runs.
+#if defined(__HIPCC__)
+#define MI355REC_HD __host__ __device__
+#define MI355REC_UNROLL _Pragma("unroll")
+#else
+#define MI355REC_HD
+#define MI355REC_UNROLL
+#endif
+constexpr int PARITY_PARTS = 16, PARITY_PART_MAX = FAST_MAX_BATCHES / PARITY_PARTS;
+struct ParityPart {
+    unsigned t[PARITY_PART_MAX];
+};
+MI355REC_HD inline int parity_part_len(int n_batches) { return (n_batches + PARITY_PARTS - 1) / PARITY_PARTS; }   // <= PARITY_PART_MAX
+// the touch words of part `part` of the column at `col` (row stride in words), and their XOR
+MI355REC_HD inline unsigned parity_load(const unsigned *col, size_t stride, int n_batches, int part, ParityPart &p) {
+    const int len = parity_part_len(n_batches), b0 = part * len;
+    unsigned total = 0;
+    MI355REC_UNROLL
+    for (int i = 0; i < PARITY_PART_MAX; ++i) {
+        const int b = b0 + i;
+        p.t[i] = i < len && b < n_batches ? col[(size_t)b * stride] : 0u;
+        total ^= p.t[i];
+    }
+    return total;
+}
+// ... replaced by the parities in front of each of the part's mini-batches; `running`: in front of the part's first
+MI355REC_HD inline void parity_store(unsigned *col, size_t stride, int n_batches, int part, const ParityPart &p, unsigned running) {
+    const int len = parity_part_len(n_batches), b0 = part * len;
+    MI355REC_UNROLL
+    for (int i = 0; i < PARITY_PART_MAX; ++i) {
+        const int b = b0 + i;
+        if (i < len && b < n_batches) col[(size_t)b * stride] = running;
+        running ^= p.t[i];
+    }
+}
+// (on the device par[] is an allocation of its own: 32 rows' bytes are 16-byte aligned and move as two 16-byte accesses)
+template <class P>
+MI355REC_HD inline P *parity_bytes(P *at) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return static_cast<P *>(__builtin_assume_aligned(at, 16));
+#else
+    return at;
+#endif
+}
+// par[] (one byte per row, 0 / 1) of rows 32 w .. 32 w + 31 as a word; the last word of a row is partial, the padding words are empty
+MI355REC_HD inline unsigned pack_parities(const unsigned char *par, long long n_entries, int w) {
+    const long long x0 = 32ll * w;
+    unsigned v = 0;
+    if (x0 + 32 <= n_entries) {
+        unsigned q[8];                        // four bytes a word: bit 0 of each byte -> one nibble
+        __builtin_memcpy(q, parity_bytes(par + x0), 32);
+    MI355REC_UNROLL
+        for (int k = 0; k < 8; ++k) v |= ((q[k] & 1u) | ((q[k] >> 7) & 2u) | ((q[k] >> 14) & 4u) | ((q[k] >> 21) & 8u)) << (4 * k);
+    } else {
+        for (int i = 0; i < 32 && x0 + i < n_entries; ++i) v |= (unsigned)(par[x0 + i] & 1) << i;
+    }
+    return v;
+}
+MI355REC_HD inline void unpack_parities(unsigned char *par, long long n_entries, int w, unsigned v) {
+    const long long x0 = 32ll * w;
+    if (x0 + 32 <= n_entries) {
+        unsigned q[8];
+    MI355REC_UNROLL
+        for (int k = 0; k < 8; ++k) {
+            const unsigned n = v >> (4 * k);
+            q[k] = (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21);
+        }
+        __builtin_memcpy(parity_bytes(par + x0), q, 32);
+    } else {
+        for (int i = 0; i < 32 && x0 + i < n_entries; ++i) par[x0 + i] = (unsigned char)((v >> i) & 1);
+    }
+}
+// one column, part after part
+inline void parity_column(unsigned *rows, int row_words, int n_batches, unsigned char *par, long long n_entries, int w) {
+    ParityPart parts[PARITY_PARTS];
+    unsigned total[PARITY_PARTS];
+    for (int part = 0; part < PARITY_PARTS; ++part) total[part] = parity_load(rows + w, (size_t)row_words, n_batches, part, parts[part]);
+    unsigned running = pack_parities(par, n_entries, w);
+    for (int part = 0; part < PARITY_PARTS; ++part) {
+        parity_store(rows + w, (size_t)row_words, n_batches, part, parts[part], running);
+        running ^= total[part];
+    }
+    unpack_parities(par, n_entries, w, running);
 }
 
 // pair records per mini-batch the mini-batch kernel steps over (0: it reads one mini-batch of zeros, see BufferPlan::slot_recs)
@@ -256,6 +379,7 @@ struct BufferPlan {
     size_t tasks, recs, batch_count;
     size_t slot_recs;           // (the mini-batch kernel reads a slot's pair records whatever the schedule: without the in-LDS schedule one mini-batch of zeros)
     size_t sorted_slot, qtask, used, touched;       // in-LDS schedule only (0 without it)
+    size_t bit_rows;            // in-LDS schedule on bit rows: mini-batches of one schedule x row words (`touched` is 0 then)
 };
 inline BufferPlan buffer_plan(const MfShape &s, const MfKnobs &knobs, size_t n_samples, long long n_batches, bool whole_stream) {
     BufferPlan b{};
@@ -276,6 +400,15 @@ inline BufferPlan buffer_plan(const MfShape &s, const MfKnobs &knobs, size_t n_s
         b.sorted_slot = b.qtask = tb * tpb;
         b.used = tb;
         b.touched = ((size_t)s.n_users + s.n_items) * (FAST_MAX_BATCHES / 32);
+    }
+    return b;
+}
+// buffer_plan with the handle's cached decision (MfShape::bit_rows): the bit rows of one schedule in place of the per-row bitmap
+inline BufferPlan buffer_plan_bit_rows(const MfShape &s, const MfKnobs &knobs, size_t n_samples, long long n_batches, bool whole_stream) {
+    BufferPlan b = buffer_plan(s, knobs, n_samples, n_batches, whole_stream);
+    if (b.fast1 && s.bit_rows) {
+        b.touched = 0;
+        b.bit_rows = (size_t)std::min<long long>(b.table_batches, FAST_MAX_BATCHES) * (size_t)bit_row_words((long long)s.n_users + s.n_items);
     }
     return b;
 }

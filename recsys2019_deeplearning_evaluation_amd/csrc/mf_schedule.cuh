@@ -130,6 +130,13 @@ __global__ __launch_bounds__(256) void mf_recs_kernel(const SchedParams s) {
 // than two rounds of one wavefront get the 4 wavefronts of a workgroup: 4 aligned headers), and one bit per (row, mini-batch) in a global bitmap;
 // (2) per incidence, the version parity of each of the sample's rows = parity at stream start + number of earlier
 // mini-batches with the row's bit set; (3) per row, the parity after the stream, bitmap cleared for the next one.
+// BIT ROWS (the default wherever a mini-batch's bit row fits LDS beside the keys: mf_plan.h, bit_rows_fit): the bitmap is stored the
+// other way round, [mini-batch][row bit].  (1) collects the mini-batch's row in LDS and writes it out once -- no global atomic, nothing
+// to clear; (2') one pass down the word columns, mf_sched_parity_kernel, turns touch bits into version parities in place and moves
+// par[] to the end of the stream; (3') the emit kernel reads one word per row.  Headers, records, pair records, used[], the stream
+// and par[] after a stream are byte for byte those of the per-row bitmap, which remains for larger shapes and under
+// MI355REC_MF_ROW_BITMAP: `touched`, one device-scope atomicOr per run (375 k per epoch at the ML-20M shape, the whole 18.7 us of
+// the sort kernel's "headers" phase), row_bits / version_parity in the emit kernel, and the finish kernel behind it.
 // (The limits FAST_MAX_BATCHES / FAST_MAX_SLOTS, the layout of header.meta and of qtask[], SCHED_THREADS and SCHED_STAMPS: mf_plan.h.)
 
 struct FastSchedParams {
@@ -143,8 +150,8 @@ struct FastSchedParams {
     int *su, *si, *sj;
     float *sr;
     // draw = 1: the sort kernel's workgroups DRAW their mini-batch (mf_draw_sample: sample t of epoch e is a pure function of seed, e
-    // and t) and store it to su/si/sj/sr, instead of reading back what a sampler launch in front of them wrote; the finish kernel
-    // then advances the epoch counter (advance_epoch = 1) -- never a kernel that reads it, whose later workgroups would see the next
+    // and t) and store it to su/si/sj/sr, instead of reading back what a sampler launch in front of them wrote; the parity kernel
+    // (per-row bitmap: the finish kernel) then advances the epoch counter (advance_epoch = 1) -- never a kernel that reads it, whose later workgroups would see the next
     // epoch.  Zero for replayed streams, schedule parts of a long stream, the group and the exact multi-GPU mode.
     int draw, advance_epoch, bpr, sample_negatives, n_items;
     float quota;
@@ -154,7 +161,11 @@ struct FastSchedParams {
     const int *indptr, *indices;
     const float *data;
     unsigned long long *ticks;    // optional [n_batches][SCHED_STAMPS] shader-clock stamps of the sort kernel's phases (thread 0 of every workgroup)
-    unsigned *touched;            // [n_entries][words]: bit b of row x = mini-batch b of this stream touches x
+    unsigned *touched;            // [n_entries][words]: bit b of row x = mini-batch b of this stream touches x (NULL with bit rows)
+    // bit rows (NULL: the per-row bitmap above): [n_batches][row_words], bit x of row b = mini-batch b touches row x as the sort kernel
+    // leaves it; = buffer of row x's version in front of mini-batch b once the parity kernel has run
+    unsigned *bit_rows;
+    int row_words;
     unsigned char *par;           // [n_entries]: buffer of every row's current version at stream start
     int *sorted_slot;             // [n_batches][tasks_per_batch]: per batch-local incidence (sample * per + role) its position in (row, id) order | also << 16
     int *qtask;                   // per sorted position: batch-local slot of its task's (first) header | wide << 30
@@ -201,9 +212,14 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         if (s.ticks && tid == 0) s.ticks[(size_t)b * SCHED_STAMPS + phase] = stamp();
     };
     mark(0);
+    // the mini-batch's bit row, behind the once-touched flags (its zeroes are published by the barrier behind the keys)
+    unsigned *bits = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(sched_lds) + sizeof(unsigned) * (size_t)np + s.mid_bytes + (size_t)np + 16);
+    const bool bit_rows = s.bit_rows != nullptr;
+    if (bit_rows)
+        for (int w = tid; w < s.row_words; w += SCHED_THREADS) bits[w] = 0;
     if (s.draw) {
         // the workgroup draws its own mini-batch: the keys come from registers, the stream is stored for the emit kernel,
-        // last_epoch_samples() and the oracle replay (the epoch word is read here and advanced by the finish kernel)
+        // last_epoch_samples() and the oracle replay (the epoch word is read here and advanced by the parity / finish kernel)
         const unsigned long long sid0 = (unsigned long long)(s.state->epoch * s.samples_per_epoch + s.first_sample + first);
         for (int smp = tid; smp < n_in; smp += SCHED_THREADS) {
             int u, i, third;
@@ -313,7 +329,9 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         const int start = hpos[t], len = hpos[t + 1] - start;
         const bool wide = len > wide_min;
         const int entry = (int)(K[start] >> sb);
-        atomicOr(&s.touched[(size_t)entry * s.words + (b >> 5)], 1u << (b & 31));      // (rows without a task advance a version, too)
+        // (rows without a task advance a version, too)
+        if (bit_rows) atomicOr(&bits[entry >> 5], 1u << (entry & 31));
+        else atomicOr(&s.touched[(size_t)entry * s.words + (b >> 5)], 1u << (b & 31));
         const bool pair = len == 1 && paired(start);
         if (absorbed(t) || (pair && start % s.group != 0)) {
             ++aoff;
@@ -335,6 +353,11 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     for (int slot = used + tid; slot < fill_end; slot += SCHED_THREADS)
         *reinterpret_cast<int4 *>(out + slot) = make_int4(0, 0, 0, 0);          // no samples: the slot's wavefront idles
     __syncthreads();
+    if (bit_rows) {                                   // the whole row, padding included, 16 bytes a lane: nothing is ever cleared
+        const uint4 *src = reinterpret_cast<const uint4 *>(bits);
+        uint4 *dst = reinterpret_cast<uint4 *>(s.bit_rows + (size_t)b * s.row_words);
+        for (int w = tid; w < s.row_words / 4; w += SCHED_THREADS) dst[w] = src[w];
+    }
     mark(6);
     for (int q = tid; q < m; q += SCHED_THREADS) {
         int lo = 0, hi = total;                       // last run starting at or before q
@@ -387,6 +410,9 @@ __device__ __forceinline__ int version_parity(const RowBits &r, int par, int b) 
 // the three rows' bitmaps and start parities, the incidences' qtask words and those of their aligned blocks' first positions.  The
 // qtask word carries what used to be read from the header (offset within the run, "first of a pair task"); only the own-row
 // buffer bit of a run's first incidence still costs a third trip, the header's meta word.
+// BIT_ROWS: the parity kernel has run in front; a row's buffer bit is bit x of the mini-batch's bit row -- three 4-byte loads in the second
+// trip in place of six 16-byte loads, three byte loads and the popcounts.
+template <bool BIT_ROWS>
 __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
     const int b = blockIdx.y, smp = blockIdx.x * 256 + threadIdx.x;
     const long long first = (long long)b * s.batch_size;
@@ -404,8 +430,16 @@ __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
     for (int role = 0; role < 3; ++role) where[role] = s.sorted_slot[base + (size_t)smp * s.per + (role < s.per ? role : 0)];
     const int third = three ? j : rating;
     const int ej = s.n_users + (three ? j : i);          // (FunkSVD: no third row; the item's again, unused)
-    const RowBits bu = row_bits(s, u), bi = row_bits(s, s.n_users + i), bj = row_bits(s, ej);
-    const int su0 = s.par[u], si0 = s.par[s.n_users + i], sj0 = s.par[ej];
+    RowBits bu, bi, bj;
+    int su0 = 0, si0 = 0, sj0 = 0;
+    unsigned wu = 0, wi = 0, wj = 0;
+    if constexpr (BIT_ROWS) {
+        const unsigned *row = s.bit_rows + (size_t)b * s.row_words;
+        wu = row[u >> 5]; wi = row[(s.n_users + i) >> 5]; wj = row[ej >> 5];
+    } else {
+        bu = row_bits(s, u); bi = row_bits(s, s.n_users + i); bj = row_bits(s, ej);
+        su0 = s.par[u]; si0 = s.par[s.n_users + i]; sj0 = s.par[ej];
+    }
     const int gmask = s.group - 1, gshift = s.group >> 1;       // group is 1, 2 or 4 (samples_in_flight)
     int tps[3], tps0[3];
 #pragma unroll
@@ -414,8 +448,16 @@ __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
         tps[role] = s.qtask[base + q];
         tps0[role] = s.qtask[base + (q & ~gmask)];
     }
-    const int pu = version_parity(bu, su0, b), pi = version_parity(bi, si0, b);
-    const int pj = three ? version_parity(bj, sj0, b) : 0;
+    int pu, pi, pj;
+    if constexpr (BIT_ROWS) {
+        pu = (int)((wu >> (u & 31)) & 1u);
+        pi = (int)((wi >> ((s.n_users + i) & 31)) & 1u);
+        pj = three ? (int)((wj >> (ej & 31)) & 1u) : 0;
+    } else {
+        pu = version_parity(bu, su0, b);
+        pi = version_parity(bi, si0, b);
+        pj = three ? version_parity(bj, sj0, b) : 0;
+    }
     const int par_bits = (pu << 2) | (pi << 3) | (pj << 4);
 #pragma unroll
     for (int role = 0; role < 3; ++role) {
@@ -451,7 +493,43 @@ __device__ __forceinline__ void mf_sched_emit_body(const FastSchedParams &s) {
     }
 }
 
-__global__ __launch_bounds__(256) void mf_sched_emit_kernel(const FastSchedParams s) { mf_sched_emit_body(s); }
+// (a scalar branch on a kernel argument in front of everything: each side stays straight-line)
+__device__ __forceinline__ void mf_sched_emit_either(const FastSchedParams &s) {
+    if (s.bit_rows) mf_sched_emit_body<true>(s);
+    else mf_sched_emit_body<false>(s);
+}
+__global__ __launch_bounds__(256) void mf_sched_emit_kernel(const FastSchedParams s) { mf_sched_emit_either(s); }
+
+// The column pass over the bit rows (mf_plan.h: parity_load / parity_store), launched BETWEEN sort and emit in place of the finish
+// kernel: a workgroup is 64 word columns (a lane each: a row of 256 bytes per access) x PARITY_PARTS wavefronts, each with one part of
+// the stream's mini-batches.  One trip fetches a wavefront's touch words (and, wavefront 0, the 32 start parities of every column);
+// the parts' XORs meet in LDS; a second round of stores leaves the parities and par[] after the stream.  No trip depends on another
+// mini-batch's.
+// Thread 0 advances the epoch word for the sort kernel's workgroups, who drew from it and have all retired (this is the next launch
+// in the stream); nothing in this kernel or behind it in the schedule reads the word.
+constexpr int PARITY_THREADS = 64 * PARITY_PARTS;
+__device__ __forceinline__ void mf_sched_parity_body(const FastSchedParams &s, const int n_batches) {
+    __shared__ unsigned part_xor[PARITY_PARTS + 1][64];         // [PARITY_PARTS]: the start parities
+    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+    if (s.advance_epoch && blockIdx.x == 0 && threadIdx.x == 0) s.state->epoch += 1;
+    const int w = blockIdx.x * 64 + lane;
+    const bool live = w < s.row_words;
+    unsigned *col = s.bit_rows + w;
+    ParityPart p;
+    unsigned total = 0;
+    if (live) {
+        total = parity_load(col, (size_t)s.row_words, n_batches, part, p);
+        if (part == 0) part_xor[PARITY_PARTS][lane] = pack_parities(s.par, s.n_entries, w);
+    }
+    part_xor[part][lane] = total;
+    __syncthreads();
+    if (!live) return;
+    unsigned running = part_xor[PARITY_PARTS][lane];
+    for (int q = 0; q < part; ++q) running ^= part_xor[q][lane];
+    parity_store(col, (size_t)s.row_words, n_batches, part, p, running);
+    if (part == PARITY_PARTS - 1) unpack_parities(s.par, s.n_entries, w, running ^ total);
+}
+__global__ __launch_bounds__(PARITY_THREADS) void mf_sched_parity_kernel(const FastSchedParams s, const int n_batches) { mf_sched_parity_body(s, n_batches); }
 
 __device__ __forceinline__ void mf_sched_finish_body(const FastSchedParams &s) {
     const int x = blockIdx.x * 256 + threadIdx.x;
