@@ -550,6 +550,15 @@ int mi355rec_ease_set_diagonal(mi355rec_ease_t h, const float *diag);
 /* The matrix <- its inverse, in place.  MI355REC_E_NUMERIC when a pivot is <= 0 or NaN -- the matrix is not positive definite;
  * mi355rec_last_error() names the step, the content of the matrix is then undefined and a new one has to be set. */
 int mi355rec_ease_invert(mi355rec_ease_t h);
+/* The same for any non-singular matrix, symmetric or not: blocked Gauss-Jordan elimination with partial (row) pivoting in float64 on
+ * a float64 working copy (8 bytes per cell of the padded matrix, allocated at the first call and freed with the handle), the result
+ * rounded to float32 into the matrix.  Preconditions and status as mi355rec_ease_invert; MI355REC_E_NUMERIC when a pivot is 0 or NaN
+ * -- the matrix is singular; MI355REC_E_UNSUPPORTED, with the matrix untouched and nothing allocated, when the working copy does not
+ * fit the device's free memory or is larger than MI355REC_EASE_PIVOT_MAX_BYTES (read at the first call of a handle). */
+int mi355rec_ease_invert_pivoted(mi355rec_ease_t h);
+/* Of the last mi355rec_ease_invert_pivoted: the swaps that moved a row, the smallest |pivot| of the pivot search, device milliseconds of
+ * pivot search + row swaps and of the update GEMM.  MI355REC_E_INVALID when none has run on the matrix that is set. */
+int mi355rec_ease_pivot_info(mi355rec_ease_t h, int32_t *moved_rows, double *min_pivot, double *pivot_ms, double *update_ms);
 /* W[i * ld + j] = P[i][j] / -P[j][j], 0 on the diagonal (host, row-major).  Needs a successful invert, else MI355REC_E_INVALID. */
 int mi355rec_ease_get_dense(mi355rec_ease_t h, float *W, int64_t ld);
 /* Per column of W its topK largest NON-ZERO cells by value (similarityMatrixTopK, Base/Recommender_utils.py:55): idx / val

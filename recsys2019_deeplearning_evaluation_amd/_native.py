@@ -183,6 +183,8 @@ SIGNATURES = {
     "mi355rec_ease_get_matrix": (C.c_int, [_vp, _vp, _i64]),
     "mi355rec_ease_set_diagonal": (C.c_int, [_vp, _vp]),
     "mi355rec_ease_invert": (C.c_int, [_vp]),
+    "mi355rec_ease_invert_pivoted": (C.c_int, [_vp]),
+    "mi355rec_ease_pivot_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_f64)]),
     "mi355rec_ease_get_dense": (C.c_int, [_vp, _vp, _i64]),
     "mi355rec_ease_get_topk": (C.c_int, [_vp, _i32, _vp, _vp]),
     "mi355rec_ease_fit_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f64), C.POINTER(_f64),

@@ -10,11 +10,13 @@
 //                       v_mfma_f32_32x32x2_f32 (128 x 128 tiles, operands staged in LDS as score_gemm_kernel does)
 //   ease_writeback_kernel  block row k <- R, block column k <- ND, the block itself <- D (replacing what the update left there)
 // Every dependency is a kernel boundary on the handle's stream; a set status word turns every later kernel into an empty launch.
+// Matrices that are not positive definite: ease_pivot.hip inverts them on the same handle (ease_handle.h) with pivoting, in float64.
 //
 // Edges: the matrix lives in an npad x npad buffer, npad = n rounded up to 128, whose tail carries an identity block.  The padded
 // matrix is block diagonal, so the leading n x n cells of its inverse are G^-1 exactly and no kernel forms an address outside the
 // buffer: every tile and every panel is whole.
 #include "common.h"
+#include "ease_handle.h"
 #include "score.h"
 #include "topk.cuh"
 
@@ -27,12 +29,10 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int TILE = 128;           // cells of a side of the update kernel's tile; the matrix is padded to a multiple of it
+constexpr int TILE = EASE_TILE;     // cells of a side of the update kernel's tile; the matrix is padded to a multiple of it
 constexpr int TK = 32;              // K chunk of the update kernel staged in LDS
 constexpr int LDT = TILE + 4;       // leading dimension of its [k][row] operand tiles: rows stay 16-byte aligned
 constexpr int PANEL_W = 64;         // columns (rows) of the panels one workgroup of ease_panel_kernel handles
-
-enum { ST_EMPTY = 0, ST_MATRIX, ST_FAILED, ST_INVERTED, ST_WEIGHTS };
 
 // D = A[k0 .. k0 + NB, k0 .. k0 + NB]^-1 in float64, by Gauss-Jordan without pivoting.  The block lives in registers, a P x P patch
 // per thread (32 x 32 threads); sweep j needs the old column j and row j of the block, which their owners publish in LDS -- two
@@ -297,17 +297,7 @@ __global__ __launch_bounds__(THREADS) void ease_topk_kernel(const float *W, int6
 
 }  // namespace
 
-struct mi355rec_ease : Handle {     // `timer`: around the elimination; `call_timer`: around the weights + top-K kernels
-    int n = 0, npad = 0, block = 0, steps = 0, failed_step = -1, state = ST_EMPTY;
-    DeviceBuffer<float> A, D, R, Ct, ND, diag, out_val;
-    DeviceBuffer<int> status, out_idx;
-    double invert_ms = 0, gram_ms = 0, topk_ms = 0;
-    int64_t launches = 0;
-
-    ~mi355rec_ease() { shutdown(); }
-};
-
-namespace {
+namespace {        // (the handle struct: ease_handle.h)
 
 size_t ease_bytes(int64_t n, int64_t npad, int block) {
     // the matrix, the three panels and the diagonal block, and -- where n is not a multiple of the tile -- the slab in which
@@ -323,6 +313,7 @@ void clear_and_pad(mi355rec_ease *h) {
         MI_HIP(hipGetLastError());
     }
     h->failed_step = -1;
+    h->pivot.valid = false;
 }
 
 template <int NB>

@@ -10,7 +10,8 @@ hot path) and the division of every column by its own diagonal entry.
 from the similarity handle straight into an `MI355XEase` handle, is inverted there in place by an unpivoted blocked elimination,
 scaled, and reduced to its column-wise top-K; only W (or its top-K slabs) is downloaded.  That elimination is for positive-definite
 matrices -- every binary or normalised URM -- and says so when the matrix is not (explicit ratings: the reference puts the
-number of stored cells, not the sum of squares, on the diagonal); the fit then finishes with the host inverse of the class above.
+number of stored cells, not the sum of squares, on the diagonal); the fit then finishes with the host inverse of the class above
+or, with `indefinite="device"`, with a pivoted float64 elimination on the device (csrc/ease_pivot.hip).
 """
 import ctypes as C
 import time
@@ -118,8 +119,19 @@ class MI355XEase(N.Handle):
             raise ValueError("the diagonal must have %d entries, got %r" % (self.n_items, d.shape))
         self._call("set_diagonal", N.ptr(d))
 
-    def invert(self):
-        self._call("invert")
+    def invert(self, pivoted=False):
+        """The matrix <- its inverse.  pivoted=False: the unpivoted float32 elimination, positive-definite input only.  pivoted=True:
+        partial pivoting in float64 (csrc/ease_pivot.hip) for any non-singular matrix; FloatingPointError when it is singular,
+        NotImplementedError -- the matrix untouched -- when the float64 working copy does not fit the device."""
+        self._call("invert_pivoted" if pivoted else "invert")
+
+    def pivot_info(self):
+        """Of the last invert(pivoted=True): swaps that moved a row, the smallest |pivot|, device milliseconds of pivot search + row
+        swaps and of the update GEMM."""
+        moved = C.c_int32()
+        f = [C.c_double() for _ in range(3)]
+        self._call("pivot_info", C.byref(moved), *[C.byref(x) for x in f])
+        return {"moved_rows": moved.value, "min_pivot": f[0].value, "pivot_ms": f[1].value, "update_ms": f[2].value}
 
     def get_dense(self):
         """W = P / (-diag P) with a zero diagonal, float32 (n_items, n_items)."""
@@ -151,13 +163,20 @@ class _EASELogic:
     `fit_info` says where the inverse ran ("device", or "host" with the reason and the elimination step that refused) and where the
     model is scored ("scoring").  `dense_scoring` decides that for the dense W of topK=None: "host" (the default: the recommender
     base multiplies on the host) or "device" (MI355XDenseScorer, the same scores bit for bit).  A sparse W is
-    scored by the device sparse scorer either way."""
+    scored by the device sparse scorer either way.  `indefinite` decides where a matrix the unpivoted elimination refuses (explicit
+    ratings) is inverted: "host" (the default: float32 `np.linalg.inv`) or "device" (the pivoted float64 elimination of
+    csrc/ease_pivot.hip; `fit_info["inverse"] == "device-pivoted"`, with `reason` the unpivoted refusal, `unpivoted_s` what that
+    attempt cost and `pivot` the handle's pivot_info()).  A pivoted inverse that refuses -- singular, NaN, no memory for the float64
+    copy -- ends on the host like the default, with `pivoted_reason` beside `reason`."""
 
     RECOMMENDER_NAME = "EASE_R_MI355X_Recommender"         # (saved models and logs tell the two classes apart)
 
-    def __init__(self, URM_train, verbose=True, dense_scoring="host"):
+    def __init__(self, URM_train, verbose=True, dense_scoring="host", indefinite="host"):
         if dense_scoring not in ("host", "device"):
             raise ValueError('dense_scoring must be "host" or "device", got {!r}'.format(dense_scoring))
+        if indefinite not in ("host", "device"):
+            raise ValueError('indefinite must be "host" or "device", got {!r}'.format(indefinite))
+        self.indefinite = indefinite
         if dense_scoring == "device" and not isinstance(self, GpuSimilarityScoringMixin):
             raise ValueError('dense_scoring="device" needs the device-scoring mixin (reference_binding.bind(..., device_scoring=True))')
         super(_EASELogic, self).__init__(URM_train, verbose=verbose)
@@ -184,11 +203,28 @@ class _EASELogic:
             self.similarity_stats = builder.stats()
             ease.set_diagonal(diagonal)
             t_filled = time.perf_counter()
+            weights = None
             try:
                 ease.invert()
                 info = dict(ease.fit_info(), inverse="device", reason="")
+            except FloatingPointError as exc:
+                # not positive definite.  The failed elimination has destroyed the matrix: the Gram matrix is built again (milliseconds)
+                # instead of keeping a second n x n copy
+                info = dict(ease.fit_info(), inverse="host", reason=str(exc))
+                unpivoted_s = time.perf_counter() - t_filled
+                ease.set_gram_from(builder)
+                ease.set_diagonal(diagonal)
+                if self.indefinite == "device":
+                    info["unpivoted_s"] = unpivoted_s           # what the refused attempt cost
+                    try:
+                        ease.invert(pivoted=True)
+                        info.update(ease.fit_info(), inverse="device-pivoted", unpivoted_failed_step=info["failed_step"], pivot=ease.pivot_info())
+                    except (FloatingPointError, NotImplementedError) as pivoted_exc:       # singular, NaN, or no memory for the float64 copy
+                        info["pivoted_reason"] = str(pivoted_exc)
+                        ease.set_gram_from(builder)
+                        ease.set_diagonal(diagonal)
+            if info["inverse"] != "host":
                 t_inverted = time.perf_counter()
-                weights = None
                 if topK is not None:
                     try:
                         idx, val = ease.get_topk(min(int(topK), n_items))
@@ -200,12 +236,8 @@ class _EASELogic:
                     if self.dense_scoring == "device":       # the scorer takes the weights where they stand: no second trip over PCIe
                         self._get_dense_scorer(weights_from=ease)
                 info["topk_ms"] = ease.fit_info()["topk_ms"]
-            except FloatingPointError as exc:
-                # not positive definite.  The failed elimination has destroyed the matrix: the Gram matrix is built again (milliseconds)
-                # instead of keeping a second n x n copy, and the reference's pivoted float32 inverse finishes on the host
-                info = dict(ease.fit_info(), inverse="host", reason=str(exc))
-                ease.set_gram_from(builder)
-                ease.set_diagonal(diagonal)
+            else:
+                # the reference's pivoted float32 inverse finishes on the host
                 gram = ease.get_matrix()
                 precision = np.linalg.inv(gram)
                 weights = precision / -precision.diagonal()              # column j over -P[j, j]
