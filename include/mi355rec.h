@@ -774,6 +774,23 @@ int mi355rec_eval_add_dscorer_candidates(mi355rec_eval_t h, mi355rec_dscorer_t s
 int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *item_counts);
 /* out[(p * n_cutoffs + c) * MI355REC_EVAL_VALUES + v]: the per-user values of the last evaluation, p = position of the user. */
 int mi355rec_eval_get_per_user(mi355rec_eval_t h, double *out);
+/* DIVERSITY_SIMILARITY (metrics.py:641-694 Diversity_similarity, Evaluator.py:353-354).  matrix: the dense item diversity matrix,
+ * n_items x n_items cells of elem_bytes (4: float32, 8: float64), row-major, host memory; indexed [row = items[i], column = items[j]]
+ * and not assumed symmetric.  Waits for the blocks under way, uploads the cells and checks on the device that every one lies in
+ * [0, 1] (MI355REC_E_INVALID otherwise, NaN included; the matrix is then not kept).  MI355REC_E_UNSUPPORTED when the lists are more
+ * than 1024 wide.  matrix == NULL takes the matrix away.  Either way the change holds from the next mi355rec_eval_begin on: with a
+ * matrix set, begin zeroes a buffer of [n_eval][n_cutoffs] float64 values of its own, every add_* call fills the rows of its users
+ * (for one user and cutoff, with `items` the first L = min(cutoff, list length) entries:
+ *     sum over i = 0 .. L-2, j = 0 .. L-1, j != i of matrix[items[i]][items[j]], divided by L (L - 1);
+ * NaN where L < 2, the reference divides by zero there), and finish sums them in a fixed order.  MI355REC_EVAL_VALUES, the layout of
+ * mi355rec_eval_finish's sums and of mi355rec_eval_get_per_user are not affected. */
+int mi355rec_eval_set_diversity(mi355rec_eval_t h, const void *matrix, int32_t elem_bytes);
+/* After mi355rec_eval_finish of an evaluation begun with a matrix set: sums[c] over the evaluated users, cutoffs in the given order;
+ * per_user (NULL, or [n_eval][n_cutoffs]) the values themselves. */
+int mi355rec_eval_get_diversity(mi355rec_eval_t h, double *sums, double *per_user);
+/* elem_bytes of the matrix that is set (0: none) and the host time of the last mi355rec_eval_set_diversity: allocation + upload, and
+ * the range check with its read-back. */
+int mi355rec_eval_diversity_info(mi355rec_eval_t h, int32_t *elem_bytes, double *upload_ms, double *check_ms);
 void mi355rec_eval_destroy(mi355rec_eval_t h);
 
 #ifdef __cplusplus

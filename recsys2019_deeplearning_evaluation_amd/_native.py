@@ -238,6 +238,9 @@ SIGNATURES = {
     "mi355rec_eval_add_itemscorer_candidates": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "mi355rec_eval_finish": (C.c_int, [_vp, _vp, _vp]),
     "mi355rec_eval_get_per_user": (C.c_int, [_vp, _vp]),
+    "mi355rec_eval_set_diversity": (C.c_int, [_vp, _vp, _i32]),
+    "mi355rec_eval_get_diversity": (C.c_int, [_vp, _vp, _vp]),
+    "mi355rec_eval_diversity_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_f64), C.POINTER(_f64)]),
     "mi355rec_eval_destroy": (None, [_vp]),
 }
 

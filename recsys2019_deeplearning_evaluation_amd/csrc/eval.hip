@@ -13,16 +13,22 @@
 // `ranked` buffer in place) or from the host (the lists path).  For the reference's EvaluatorNegativeItemSample (Evaluator.py:455-539)
 // the scorers rank each user's candidate row only (ScorerHandle::enqueue_candidates; the rows are uploaded once by
 // mi355rec_eval_set_candidates); the metric kernel and finish are the same.
+// With an item diversity matrix set (mi355rec_eval_set_diversity) every metric launch is followed, on the same stream and in front of
+// the `done` event, by eval_diversity_kernel (eval_diversity.cuh): DIVERSITY_SIMILARITY into a buffer of its own, summed by
+// eval_sum_kernel in finish.
 #include "common.h"
 #include "score.h"
 #include "itemscore.h"
 #include "wave.cuh"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <memory>
 
 #pragma clang fp contract(off)
+
+#include "eval_diversity.cuh"
 
 namespace mi355rec {
 namespace {
@@ -232,6 +238,12 @@ struct mi355rec_eval : Handle {
     DeviceBuffer<unsigned char> allowed;
     DeviceBuffer<int> cand_ptr, cand_idx;       // candidate rows of every user (mi355rec_eval_set_candidates)
     int cand_longest = -1;                      // -1: no candidate rows
+    DeviceBuffer<unsigned char> div_matrix;     // item diversity matrix, n_items x n_items cells of div_elem bytes (mi355rec_eval_set_diversity)
+    DeviceBuffer<unsigned long long> div_bad;
+    DeviceBuffer<double> div_vals, div_sums;    // [n_eval][n_cut] per-user values of the evaluation, [n_cut] their sums
+    int div_elem = 0;                           // 0: no matrix
+    bool div_begun = false, div_finished = false;
+    double div_upload_ms = 0.0, div_check_ms = 0.0;
 
     ~mi355rec_eval() {
         shutdown([&] {
@@ -259,6 +271,14 @@ void launch_metrics(mi355rec_eval *h, hipStream_t s, const int *ranked, int firs
     MI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(eval_metric_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL(eval_metric_kernel, dim3(n), dim3(64), lds, s, p);
     MI_HIP(hipGetLastError());
+    if (h->div_begun) {
+        DivParams d{};
+        d.n_items = h->n_items; d.width = h->width; d.n_cut = h->n_cut; d.first = first;
+        d.cut = h->cut.ptr; d.ranked = ranked; d.matrix = h->div_matrix.ptr; d.vals = h->div_vals.ptr;
+        if (h->div_elem == 4) launch_diversity_typed<float>(d, n, s);
+        else launch_diversity_typed<double>(d, n, s);
+        MI_HIP(hipGetLastError());
+    }
     MI_HIP(hipEventRecord(h->done, s));
 }
 
@@ -378,6 +398,9 @@ extern "C" int mi355rec_eval_begin(mi355rec_eval_t h, const double *novelty_term
         h->popularity.upload(popularity_term, h->n_items, s);
         h->vals.alloc_zero((size_t)n_eval * h->n_cut * NV, s);
         h->counts.alloc_zero((size_t)h->n_sorted * h->n_items, s);
+        h->div_begun = h->div_elem != 0;
+        h->div_finished = false;
+        if (h->div_begun) h->div_vals.alloc_zero(evalplan::div_value_cells(n_eval, h->n_cut), s);
         MI_HIP(hipStreamSynchronize(s));
         MI_HIP(hipEventRecord(h->done, s));
     });
@@ -478,12 +501,17 @@ extern "C" int mi355rec_eval_finish(mi355rec_eval_t h, double *sums, int32_t *it
         if (h->sums.count < (size_t)h->n_cut * NV) h->sums.alloc((size_t)h->n_cut * NV);
         hipLaunchKernelGGL(eval_sum_kernel, dim3(h->n_cut * NV), dim3(256), 0, s, h->vals.ptr, h->n_eval, h->n_cut * NV, h->sums.ptr);
         hipLaunchKernelGGL(eval_counts_kernel, dim3(div_up(h->n_items, 256)), dim3(256), 0, s, h->counts.ptr, h->n_sorted, h->n_items);
+        if (h->div_begun) {
+            if (h->div_sums.count < (size_t)h->n_cut) h->div_sums.alloc(h->n_cut);
+            hipLaunchKernelGGL(eval_sum_kernel, dim3(h->n_cut), dim3(256), 0, s, h->div_vals.ptr, h->n_eval, h->n_cut, h->div_sums.ptr);
+        }
         MI_HIP(hipGetLastError());
         std::vector<int> sorted_counts((size_t)h->n_sorted * h->n_items);
         h->sums.download(sums, (size_t)h->n_cut * NV, s);
         h->counts.download(sorted_counts.data(), sorted_counts.size(), s);
         MI_HIP(hipStreamSynchronize(s));
         MI_HIP(hipEventRecord(h->done, s));
+        h->div_finished = h->div_begun;
         for (int c = 0; c < h->n_cut; ++c) {            // (bucket rows are in ascending cutoff order, the output in the given one)
             const int b = (int)(std::lower_bound(h->sorted_host.begin(), h->sorted_host.end(), h->cut_host[c]) - h->sorted_host.begin());
             std::memcpy(item_counts + (size_t)c * h->n_items, sorted_counts.data() + (size_t)b * h->n_items, sizeof(int) * h->n_items);
@@ -498,6 +526,81 @@ extern "C" int mi355rec_eval_get_per_user(mi355rec_eval_t h, double *out) {
         ensure_device();
         MI_HIP(hipEventSynchronize(h->done));
         MI_HIP(hipMemcpy(out, h->vals.ptr, sizeof(double) * (size_t)h->n_eval * h->n_cut * NV, hipMemcpyDeviceToHost));
+    });
+}
+
+// The item diversity matrix of DIVERSITY_SIMILARITY: uploaded in chunks, its range checked by a device reduction.  It takes effect with
+// the next mi355rec_eval_begin.
+extern "C" int mi355rec_eval_set_diversity(mi355rec_eval_t h, const void *matrix, int32_t elem_bytes) {
+    return guarded([&] {
+        using namespace evalplan;
+        using clock = std::chrono::steady_clock;
+        const auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        MI_REQUIRE(h, "NULL argument");
+        ensure_device();
+        hipStream_t s = h->stream;
+        if (!matrix) {
+            MI_HIP(hipEventSynchronize(h->done));       // (a block still running may read the matrix)
+            h->div_elem = 0;
+            h->div_begun = h->div_finished = false;     // (an evaluation under way goes on without the metric)
+            h->div_matrix.release();
+            return;
+        }
+        MI_REQUIRE(div_elem_ok(elem_bytes), "item diversity matrix cells of %d bytes: 4 (float32) or 8 (float64)", elem_bytes);
+        if (!div_width_ok(h->width))
+            fail(MI355REC_E_UNSUPPORTED, "DIVERSITY_SIMILARITY on lists of %d entries: at most %d", h->width, DIV_MAX_WIDTH);
+        MI_HIP(hipEventSynchronize(h->done));
+        h->div_elem = 0;
+        h->div_begun = h->div_finished = false;
+        const uint64_t cells = div_matrix_cells(h->n_items), bytes = div_matrix_bytes(h->n_items, elem_bytes);
+        const auto t0 = clock::now();
+        if (h->div_matrix.count != bytes) h->div_matrix.alloc(bytes);
+        for (uint64_t c = 0; c < div_upload_chunks(bytes); ++c) {
+            const uint64_t at = c * DIV_UPLOAD_CHUNK, n = std::min<uint64_t>(DIV_UPLOAD_CHUNK, bytes - at);
+            MI_HIP(hipMemcpyAsync(h->div_matrix.ptr + at, static_cast<const unsigned char *>(matrix) + at, n, hipMemcpyHostToDevice, s));
+        }
+        MI_HIP(hipStreamSynchronize(s));
+        const auto t1 = clock::now();
+        h->div_bad.alloc_zero(1, s);
+        if (elem_bytes == 4)
+            hipLaunchKernelGGL(eval_diversity_range_kernel<float>, dim3(div_range_blocks(cells)), dim3(256), 0, s,
+                               reinterpret_cast<const float *>(h->div_matrix.ptr), (unsigned long long)cells, h->div_bad.ptr);
+        else
+            hipLaunchKernelGGL(eval_diversity_range_kernel<double>, dim3(div_range_blocks(cells)), dim3(256), 0, s,
+                               reinterpret_cast<const double *>(h->div_matrix.ptr), (unsigned long long)cells, h->div_bad.ptr);
+        MI_HIP(hipGetLastError());
+        unsigned long long bad = 0;
+        h->div_bad.download(&bad, 1, s);
+        MI_HIP(hipStreamSynchronize(s));
+        MI_HIP(hipEventRecord(h->done, s));
+        h->div_upload_ms = ms(t0, t1);
+        h->div_check_ms = ms(t1, clock::now());
+        if (bad) {
+            h->div_matrix.release();
+            fail(MI355REC_E_INVALID, "item_diversity_matrix contains value greater than 1.0 or lower than 0.0: %llu cells (NaN included)", bad);
+        }
+        h->div_elem = elem_bytes;
+    });
+}
+
+extern "C" int mi355rec_eval_get_diversity(mi355rec_eval_t h, double *sums, double *per_user) {
+    return guarded([&] {
+        MI_REQUIRE(h && sums, "NULL argument");
+        MI_REQUIRE(h->div_finished, "mi355rec_eval_finish has not been called on an evaluation with an item diversity matrix");
+        ensure_device();
+        MI_HIP(hipEventSynchronize(h->done));
+        MI_HIP(hipMemcpy(sums, h->div_sums.ptr, sizeof(double) * (size_t)h->n_cut, hipMemcpyDeviceToHost));
+        if (per_user)
+            MI_HIP(hipMemcpy(per_user, h->div_vals.ptr, sizeof(double) * evalplan::div_value_cells(h->n_eval, h->n_cut), hipMemcpyDeviceToHost));
+    });
+}
+
+extern "C" int mi355rec_eval_diversity_info(mi355rec_eval_t h, int32_t *elem_bytes, double *upload_ms, double *check_ms) {
+    return guarded([&] {
+        MI_REQUIRE(h && elem_bytes && upload_ms && check_ms, "NULL argument");
+        *elem_bytes = h->div_elem;
+        *upload_ms = h->div_upload_ms;
+        *check_ms = h->div_check_ms;
     });
 }
 

@@ -12,6 +12,11 @@ user ranks its own candidates only (its test items plus the sampled negatives), 
 Given the same lists, both give bitwise the same result, whatever the block size.  (The sparse scorer sums with LDS float atomics, so
 its order of near-tied scores, and with it a list, can change from one call to the next.)  O(n_items) population metrics (coverage, Gini, Shannon,
 Herfindahl, mean inter-list diversity) and F1 are finished here in float64 from the device's item counters.
+With a `diversity_object` (the reference's Diversity_similarity, or a dense ndarray) both evaluators add DIVERSITY_SIMILARITY
+(metrics.py:641-694): the matrix is uploaded once, at construction, and a second kernel behind the metric kernel gathers each list's
+cells from it in float64 (csrc/eval_diversity.cuh).  Where the reference raises ZeroDivisionError -- a list of fewer than two items
+at some cutoff -- so does evaluateRecommender, after the evaluation.  Deviation: the matrix's range is checked once, at construction,
+on the device (ValueError), not on every evaluation.
 """
 import ctypes as C
 import sys
@@ -31,6 +36,32 @@ METRICS = ["ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", 
 PER_USER = ["ROC_AUC", "PRECISION", "PRECISION_RECALL_MIN_DEN", "RECALL", "MAP", "MRR", "NDCG", "HIT_RATE", "ARHR", "NOVELTY",
             "AVERAGE_POPULARITY"]
 N_VALUES = len(PER_USER) + 1
+# With a diversity_object: the metric at its place in EvaluatorMetrics, after AVERAGE_POPULARITY (Evaluator.py:34-36)
+DIVERSITY_SIMILARITY = "DIVERSITY_SIMILARITY"
+METRICS_WITH_DIVERSITY = (METRICS[:METRICS.index("AVERAGE_POPULARITY") + 1] + [DIVERSITY_SIMILARITY]
+                          + METRICS[METRICS.index("AVERAGE_POPULARITY") + 1:])
+DIVERSITY_MAX_WIDTH = 1024          # csrc/eval_plan.h DIV_MAX_WIDTH
+
+
+def diversity_matrix_of(diversity_object, n_items, check_values=True):
+    """The item diversity matrix of a `diversity_object` as the device takes it: a C-contiguous n_items x n_items ndarray, float32 or
+    float64 as passed, any other real dtype as float64.  Accepted: an object with an `item_diversity_matrix` attribute (the
+    reference's Diversity_similarity, metrics.py:641-661) or a bare ndarray.  Anything else, a scipy sparse matrix and np.matrix
+    raise NotImplementedError; a wrong shape, a value outside [0, 1] and a NaN raise ValueError (the assertion of metrics.py:655-656,
+    which the reference makes in Diversity_similarity.__init__).  Needs no device.  check_values=False leaves the range to the caller:
+    the evaluators check it on the device after the upload."""
+    matrix = getattr(diversity_object, "item_diversity_matrix", diversity_object)
+    if sps.issparse(matrix) or isinstance(matrix, np.matrix) or not isinstance(matrix, np.ndarray) or matrix.dtype.kind not in "fiub":
+        raise NotImplementedError("DIVERSITY_SIMILARITY takes a dense numpy.ndarray of real numbers, or an object whose "
+                                  "`item_diversity_matrix` is one (Diversity_similarity): got {}".format(type(matrix).__name__))
+    if matrix.ndim != 2 or matrix.shape != (n_items, n_items):
+        raise ValueError("item_diversity_matrix is {}, expected {}".format(matrix.shape, (n_items, n_items)))
+    if matrix.dtype not in (np.float32, np.float64):
+        matrix = matrix.astype(np.float64)
+    matrix = np.ascontiguousarray(matrix)
+    if check_values and matrix.size and not (np.all(matrix >= 0.0) and np.all(matrix <= 1.0)):      # (a NaN fails both comparisons)
+        raise ValueError("item_diversity_matrix contains value greater than 1.0 or lower than 0.0")
+    return matrix
 
 
 def get_result_string(results_run, n_decimals=7):
@@ -126,8 +157,9 @@ class EvaluatorHoldout_MI355X(N.Handle):
                  ignore_items=None, ignore_users=None, verbose=True):
         if isinstance(URM_test_list, list):
             raise ValueError("List of URM_test not supported")
-        if diversity_object is not None:
-            raise NotImplementedError("{}: DIVERSITY_SIMILARITY (diversity_object) is not supported".format(self.EVALUATOR_NAME))
+        # (before anything touches the device; the range of the values is checked there, after the upload)
+        diversity = None if diversity_object is None else diversity_matrix_of(diversity_object, URM_test_list.shape[1], check_values=False)
+        self.metrics = METRICS if diversity is None else METRICS_WITH_DIVERSITY
         self.verbose = verbose
         self.ignore_items_flag = ignore_items is not None
         self.ignore_items_ID = np.array([]) if ignore_items is None else np.array(ignore_items)
@@ -142,6 +174,9 @@ class EvaluatorHoldout_MI355X(N.Handle):
         self.URM_test = sps.csr_matrix(URM_test_list, copy=True)
         self.n_users, self.n_items = self.URM_test.shape
         self.width = min(self.max_cutoff, self.n_items)
+        if diversity is not None and self.width > DIVERSITY_MAX_WIDTH:
+            raise NotImplementedError("{}: DIVERSITY_SIMILARITY on lists of {} entries: at most {}".format(
+                self.EVALUATOR_NAME, self.width, DIVERSITY_MAX_WIDTH))
 
         self.users_to_evaluate, mask = users_to_evaluate(self.URM_test, min_ratings_per_user, self.ignore_items_ID, ignore_users)
         if not np.all(mask):
@@ -160,7 +195,9 @@ class EvaluatorHoldout_MI355X(N.Handle):
         cutoffs = np.asarray(self.cutoff_list, dtype=np.int32)
         self._create(self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices), N.ptr(relevance), N.ptr(cutoffs), len(cutoffs),
                      N.ptr(log_table), log_len)
-        self._per_user = None
+        if diversity is not None:
+            self._call("set_diversity", N.ptr(diversity), diversity.dtype.itemsize)
+        self._per_user = self._per_user_diversity = None
         self.item_counts = None             # {cutoff: times each item was recommended within the cutoff}, last evaluation
 
     def _print(self, string):
@@ -187,13 +224,23 @@ class EvaluatorHoldout_MI355X(N.Handle):
             if n_eval == 0:
                 self._print("WARNING: No users had a sufficient number of relevant items")
                 self._per_user = np.zeros((0, len(self.cutoff_list), N_VALUES))
-                results = {c: {m: 0.0 for m in METRICS} for c in self.cutoff_list}
+                self._per_user_diversity = np.zeros((0, len(self.cutoff_list)))
+                results = {c: {m: 0.0 for m in self.metrics} for c in self.cutoff_list}    # (Diversity_similarity.get_metric_value, metrics.py:683-688)
                 return results, get_result_string(results)
             self._call("begin", N.ptr(novelty), N.ptr(popularity_norm), N.ptr(users), n_eval)
             self._run(rec, block_size)
             sums = np.zeros((len(self.cutoff_list), N_VALUES), np.float64)
             counts = np.zeros((len(self.cutoff_list), self.n_items), np.int32)
             self._call("finish", N.ptr(sums), N.ptr(counts))
+            self._per_user_diversity = None
+            diversity_sums = None
+            if self.metrics is METRICS_WITH_DIVERSITY:
+                diversity_sums = np.zeros(len(self.cutoff_list), np.float64)
+                self._call("get_diversity", N.ptr(diversity_sums), None)
+                if np.isnan(diversity_sums).any():          # (the validated matrix holds no NaN: a NaN sum means exactly a short list)
+                    raise ZeroDivisionError("{}: a list of fewer than two items met a diversity_object (cutoffs {}): float division "
+                                            "by zero in Diversity_similarity.add_recommendations".format(
+                                                self.EVALUATOR_NAME, [c for c, s in zip(self.cutoff_list, diversity_sums) if np.isnan(s)]))
         finally:
             if self.ignore_items_flag:
                 rec.reset_items_to_ignore()
@@ -204,9 +251,11 @@ class EvaluatorHoldout_MI355X(N.Handle):
             mean = dict(zip(PER_USER, sums[c, :len(PER_USER)] / n_eval))
             row = {m: float(mean[m]) for m in PER_USER}
             row["F1"] = f1_score(row["PRECISION"], row["RECALL"])
+            if diversity_sums is not None:
+                row[DIVERSITY_SIMILARITY] = float(diversity_sums[c] / n_eval)
             row.update(population_metrics(counts[c], n_eval, cutoff, self.ignore_items_ID, self.n_users, len(self.ignore_users_ID),
                                           int(sums[c, N_VALUES - 1])))
-            results[cutoff] = {m: row[m] for m in METRICS}
+            results[cutoff] = {m: row[m] for m in self.metrics}
         elapsed = time.time() - started
         self._print("Processed {} ( {:.2f}% ) in {:.2f} sec. Users per second: {:.0f}".format(
             n_eval, 100.0, elapsed, n_eval / max(elapsed, 1e-9)))
@@ -267,8 +316,16 @@ class EvaluatorHoldout_MI355X(N.Handle):
                 out = np.zeros((n_eval, len(self.cutoff_list), N_VALUES), np.float64)
                 self._call("get_per_user", N.ptr(out))
                 self._per_user = out
-        return {cutoff: {m: self._per_user[:, c, v].copy() for v, m in enumerate(PER_USER)}
-                for c, cutoff in enumerate(self.cutoff_list)}
+        values = {cutoff: {m: self._per_user[:, c, v].copy() for v, m in enumerate(PER_USER)}
+                  for c, cutoff in enumerate(self.cutoff_list)}
+        if self.metrics is METRICS_WITH_DIVERSITY:
+            if self._per_user_diversity is None:
+                out = np.zeros((len(self.users_to_evaluate), len(self.cutoff_list)), np.float64)
+                self._call("get_diversity", N.ptr(np.zeros(len(self.cutoff_list), np.float64)), N.ptr(out))
+                self._per_user_diversity = out
+            for c, cutoff in enumerate(self.cutoff_list):
+                values[cutoff][DIVERSITY_SIMILARITY] = self._per_user_diversity[:, c].copy()
+        return values
 
 
 def items_to_rank(URM_test, URM_test_negative):
