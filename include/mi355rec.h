@@ -281,7 +281,8 @@ int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *cfg, int32_
 int mi355rec_mf_run_epochs(mi355rec_mf_t h, int32_t n_epochs);
 /* Parity mode: the same arithmetic on a caller-provided sample stream, cut into consecutive mini-batches of
  * batch_size (the last one may be short but is still averaged over batch_size, like .pyx:802).
- * BPR: (u, i, j); FunkSVD: (u, i, rating) with j == NULL. */
+ * BPR: (u, i, j); FunkSVD: (u, i, rating) with j == NULL.  A user id outside [0, n_users) or an item id outside
+ * [0, n_items) is MI355REC_E_INVALID: nothing is copied or run. */
 int mi355rec_mf_run_samples(mi355rec_mf_t h, const int32_t *u, const int32_t *i, const int32_t *j,
                             const float *rating, int64_t n);
 /* Exact multi-GPU mini-batches (MF_BPR with sgd): one epoch with the tasks of every mini-batch split over

@@ -763,6 +763,15 @@ extern "C" int mi355rec_mf_run_samples(mi355rec_mf_t h, const int32_t *u, const 
         const bool bpr = h->cfg.algorithm == MI355REC_MF_BPR;
         MI_REQUIRE(bpr ? j != nullptr : rating != nullptr, "%s", bpr ? "BPR replay needs the negative items" : "FunkSVD / AsySVD replay needs the ratings");
         MI_REQUIRE(n >= 0, "n must be >= 0");
+        // the kernels index the factor matrices, the bit rows and par[] with these ids as they come: one pass on the host in front of
+        // everything (AsySVD: u is a user id there, too -- its profile is what the step walks)
+        const auto check_ids = [n](const int32_t *ids, int32_t limit, const char *what) {
+            for (int64_t t = 0; t < n; ++t)
+                if (ids[t] < 0 || ids[t] >= limit) fail(MI355REC_E_INVALID, "sample %lld: %s id %d out of range [0, %d)", (long long)t, what, ids[t], limit);
+        };
+        check_ids(u, h->n_users, "user");
+        check_ids(i, h->n_items, "item");
+        if (bpr) check_ids(j, h->n_items, "negative item");
         const MfKnobs knobs = read_mf_knobs();
         ensure_device();
         if (n == 0) return;

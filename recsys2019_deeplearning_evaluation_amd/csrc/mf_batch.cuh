@@ -188,7 +188,7 @@ __device__ __forceinline__ void mf_batch_body(const MfParams<T> &p, const int ba
     if (bias && !active) mu_eff = global_bias_finish(p, mu_req, gb, batch_local, wv == 0, lane);      // (wavefront 0 files the value either way)
     if (active) {
         const int entry = h0.x, len = h0.y & LEN_MASK, own_par = (unsigned)h0.y >> 31, start = h0.z;
-        // a wide task (list longer than two rounds of a wavefront) owns the 4 wavefronts of this workgroup: quarter `part` takes list
+        // a wide task (list_is_wide, mf_plan.h: a list longer than two rounds of a wavefront and than 3) owns the 4 wavefronts of this workgroup: quarter `part` takes list
         // positions part * G + g, then every 4 * G; h1 is the record at part * G
         const bool wide = (h0.y & META_WIDE) != 0;
         const int part = (h0.y >> 28) & 3;

@@ -18,6 +18,15 @@
 namespace mi355rec {
 namespace {
 
+// functions the kernels call, too
+#if defined(__HIPCC__)
+#define MI355REC_HD __host__ __device__
+#define MI355REC_UNROLL _Pragma("unroll")
+#else
+#define MI355REC_HD
+#define MI355REC_UNROLL
+#endif
+
 // ---- constants shared with the kernels -------------------------------------------------------------------------------------------
 // one L2 atomic per workgroup that carries global-bias terms: atomics on ONE address retire at about 0.2 us each (measured through
 // the batch kernel: 31 per address cost 3 us per mini-batch), so the terms are spread over a wavefront's worth of addresses
@@ -207,6 +216,16 @@ inline size_t sched_lds_bytes(int np, size_t sort_storage_bytes) {
     return sizeof(unsigned) * (size_t)np + sched_mid_bytes(np, sort_storage_bytes) + (size_t)np + 16;
 }
 
+// HEADER SLOTS.  A run (the incidences of one row in one mini-batch) of `len` samples is WIDE when it is longer than two rounds of one
+// wavefront, which works on `group` samples at a time (samples_in_flight): it is split over the 4 wavefronts of a workgroup and takes 4
+// aligned header slots, every other run takes one (absorbed rows and the later runs of a pair task: none).  A mini-batch has as many
+// header slots as incidences (tasks_per_batch) and the mini-batch launch one wavefront per slot, so a run must never take more slots
+// than it has incidences: header_slots(len, group) <= len.  On the instances with one sample in flight a list of 3 is therefore NOT
+// wide (it runs three rounds on one wavefront) -- with `len > 2 * group` alone it took 4 slots, and FunkSVD's mini-batch of three samples
+// with one item and three users 7 of its 6: the last header went into the next mini-batch's slots, where no wavefront of its launch ran.
+MI355REC_HD inline bool list_is_wide(int len, int group) { return len > (2 * group > 3 ? 2 * group : 3); }
+MI355REC_HD inline int header_slots(int len, int group) { return list_is_wide(len, group) ? 4 : 1; }
+
 struct FastSchedNumbers {
     int np, slot_bits, entry_bits, mid_bytes, words, group, fuse, fill_all;
     int row_words, bit_rows;    // words of a mini-batch's bit row; 1: the schedule runs on bit rows (both 0 from fast_sched_numbers)
@@ -258,13 +277,6 @@ inline FastSchedNumbers fast_sched_numbers_bit_rows(const MfShape &s, const MfKn
 // are cut into PARITY_PARTS consecutive parts of parity_part_len() each: a part's loads are independent of one another, its XOR is
 // all the later parts need of it.  The kernel gives a part to a wavefront (a lane per column, the XORs meet in LDS); parity_column()
 // walks the parts in turn -- the same functions, which is what tests/test_mf_bit_rows_plan.py runs.
-#if defined(__HIPCC__)
-#define MI355REC_HD __host__ __device__
-#define MI355REC_UNROLL _Pragma("unroll")
-#else
-#define MI355REC_HD
-#define MI355REC_UNROLL
-#endif
 constexpr int PARITY_PARTS = 16, PARITY_PART_MAX = FAST_MAX_BATCHES / PARITY_PARTS;
 struct ParityPart {
     unsigned t[PARITY_PART_MAX];

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void mf_recs_kernel(const SchedParams s) {
 // of a BPR epoch at ML-20M shape, plus 270 us for the task kernel's dependent searches) -- two thirds of the time of the 139
 // mini-batches it prepares.  When a mini-batch fits LDS and the stream has at most 256 mini-batches the same tasks come out of
 // three short kernels: (1) per mini-batch, a stable radix sort of (row, slot) keys in LDS, run lengths, task slots (lists longer
-// than two rounds of one wavefront get the 4 wavefronts of a workgroup: 4 aligned headers), and one bit per (row, mini-batch) in a global bitmap;
+// than two rounds of one wavefront -- list_is_wide, mf_plan.h -- get the 4 wavefronts of a workgroup: 4 aligned headers), and one bit per (row, mini-batch) in a global bitmap;
 // (2) per incidence, the version parity of each of the sample's rows = parity at stream start + number of earlier
 // mini-batches with the row's bit set; (3) per row, the parity after the stream, bitmap cleared for the next one.
 // BIT ROWS (the default wherever a mini-batch's bit row fits LDS beside the keys: mf_plan.h, bit_rows_fit): the bitmap is stored the
@@ -313,10 +313,11 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     const int CT = (total + SCHED_THREADS - 1) / SCHED_THREADS;
     const int t_lo = min(tid * CT, total), t_hi = min(t_lo + CT, total);
     int wcnt = 0, acnt = 0;
-    const int wide_min = 2 * s.group;               // longer than two rounds of one wavefront: split over a workgroup
+    // (list_is_wide, mf_plan.h: longer than two rounds of one wavefront and than 3: split over a workgroup.  No run takes more slots
+    // than it has incidences, so `used` below stays within tasks_per_batch.)
     for (int t = t_lo; t < t_hi; ++t) {
         const int start = hpos[t], len = hpos[t + 1] - start;
-        wcnt += len > wide_min;
+        wcnt += list_is_wide(len, s.group);
         acnt += absorbed(t) || (len == 1 && start % s.group != 0 && paired(start));      // runs without a header of their own
     }
     int woff = 0, n_wide = 0, aoff = 0, n_abs = 0;
@@ -327,7 +328,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
     TaskHeader *out = s.tasks + (size_t)b * s.tasks_per_batch;
     for (int t = t_lo; t < t_hi; ++t) {
         const int start = hpos[t], len = hpos[t + 1] - start;
-        const bool wide = len > wide_min;
+        const bool wide = list_is_wide(len, s.group);
         const int entry = (int)(K[start] >> sb);
         // (rows without a task advance a version, too)
         if (bit_rows) atomicOr(&bits[entry >> 5], 1u << (entry & 31));
@@ -341,7 +342,7 @@ __device__ __forceinline__ void mf_sched_sort_body(const FastSchedParams &s, con
         const int slot = wide ? 4 * woff : 4 * n_wide + (t - woff - aoff);
         woff += wide;
         tpos[t] = slot | (wide ? META_WIDE : 0) | (pair ? QTASK_PAIR : 0);
-        for (int part = 0; part < (wide ? 4 : 1); ++part) {
+        for (int part = 0; part < header_slots(len, s.group); ++part) {
             *reinterpret_cast<int4 *>(out + slot + part) =
                 make_int4(entry, (pair ? s.group : len) | (wide ? META_WIDE | (part << 28) : 0), b * s.tasks_per_batch + start, pair ? 1 : 0);
             out[slot + part].rec0 = make_int4(0, 0, 0, 0);     // (a short wide list leaves its last quarters without a record)

@@ -142,6 +142,18 @@ static void sort_workgroups() {
     CHECK(f.slot_bits + f.entry_bits <= 32 && f.fuse == 1 && f.group == 4 && f.words * 32 == FAST_MAX_BATCHES);
 }
 
+// a run never takes more header slots than it has incidences (a mini-batch has one slot and one wavefront per incidence); the
+// threshold of the instances with 2 and 4 samples in flight is "longer than two rounds"
+static void header_slot_rule() {
+    for (int group : {1, 2, 4})
+        for (int len = 1; len <= 8192; ++len) {
+            CHECK(header_slots(len, group) <= len);
+            CHECK(header_slots(len, group) == (list_is_wide(len, group) ? 4 : 1));
+            if (group > 1) CHECK(list_is_wide(len, group) == (len > 2 * group));
+        }
+    CHECK(!list_is_wide(3, 1) && list_is_wide(4, 1));
+}
+
 static void epochs_and_shards() {
     MfKnobs off;
     for (long long nb : {1ll, 10ll, GRAPH_SEGMENT, GRAPH_SEGMENT + 1, 20001ll, MAX_GRAPH_BATCHES}) {
@@ -194,6 +206,7 @@ int main() {
     widths();
     streams();
     sort_workgroups();
+    header_slot_rule();
     epochs_and_shards();
     integer_limits();
     if (failures) {

@@ -94,6 +94,10 @@ extern "C" void mf_sched_np(int tpb, uint64_t sort_storage_bytes, int64_t *out) 
     memcpy(out, v, sizeof(v));
 }
 
+// the header-slot rule of the in-LDS schedule for a run of `len` incidences on an instance with `group` samples in flight
+extern "C" int mf_list_is_wide(int len, int group) { return list_is_wide(len, group); }
+extern "C" int mf_header_slots(int len, int group) { return header_slots(len, group); }
+
 // out[4]: batch_bits, end_bit, end_bit <= 64, by_rank
 extern "C" void mf_general(const int64_t *s, int64_t n_batches, int64_t *out) {
     const GeneralSched g = general_sched(shape_of(s), n_batches);

@@ -406,6 +406,82 @@ def test_fast_schedule_numbers(recorded):
     assert used == {"reads_used", "not_cached", "general_schedule_set", "too_many_batches"}
 
 
+# ---- header slots of the in-LDS schedule --------------------------------------------------------------------------------------
+# (mf_plan.npz stays as it is: these two functions are compared with the restatement below)
+SLOT_GROUPS = (1, 2, 4)         # samples in flight of the instances in ROW_WIDTHS
+
+
+def is_wide(length, group):
+    """a run is split over the 4 wavefronts of a workgroup when it is longer than two rounds of one wavefront -- and than 3"""
+    return length > max(2 * group, 3)
+
+
+def slots_of(length, group):
+    return 4 if is_wide(length, group) else 1
+
+
+def parent_slots_of(length, group):
+    """the rule the sort kernel had before list_is_wide(): `len > 2 * group` alone"""
+    return 4 if length > 2 * group else 1
+
+
+def partitions(m, largest=None):
+    """every multiset of run lengths that adds up to m, largest run first"""
+    largest = m if largest is None else largest
+    if m == 0:
+        yield ()
+        return
+    for first in range(min(m, largest), 0, -1):
+        for rest in partitions(m - first, first):
+            yield (first,) + rest
+
+
+def declare_slots(lib):
+    lib.mf_list_is_wide.argtypes = lib.mf_header_slots.argtypes = [C.c_int, C.c_int]
+    return lib
+
+
+@pytest.mark.parametrize("group", SLOT_GROUPS)
+def test_a_run_takes_no_more_header_slots_than_it_has_incidences(shim, group):
+    """A mini-batch has one header slot (and its launch one wavefront) per incidence, and the sort kernel hands slots out without a
+    bound of its own: 4 * wide runs + the others.  So no run may take more slots than it has incidences.  `len > 2 * group` alone
+    breaks this at (group 1, len 3): 4 slots for 3 incidences."""
+    declare_slots(shim)
+    over = [(group, n, shim.mf_header_slots(n, group)) for n in range(1, 8193) if shim.mf_header_slots(n, group) > n]
+    assert over == [], over
+    assert all(shim.mf_header_slots(n, group) == slots_of(n, group) and shim.mf_list_is_wide(n, group) == is_wide(n, group) for n in range(1, 8193))
+
+
+@pytest.mark.parametrize("group", SLOT_GROUPS)
+def test_the_runs_of_a_mini_batch_fit_its_header_slots(shim, group):
+    """what the kernel relies on: however m incidences fall into runs, the runs' slots add up to at most m"""
+    declare_slots(shim)
+    seen = 0
+    for m in range(1, 25):
+        slots = {n: shim.mf_header_slots(n, group) for n in range(1, m + 1)}
+        for runs in partitions(m):
+            seen += 1
+            used = sum(slots[n] for n in runs)
+            assert used <= m, (group, m, runs, used)
+    assert seen == 7337            # the partition numbers p(1) + .. + p(24)
+
+
+def test_the_wide_threshold_of_the_wider_instances_is_unchanged(shim):
+    """groups 2 and 4 (rows of up to 32 chunks: the headline k = 128 in float32 among them) keep `len > 2 * group` exactly, so their
+    schedules stay what they were bit for bit; group 1 differs from it at len 3 alone"""
+    declare_slots(shim)
+    for group in (2, 4):
+        assert all(shim.mf_list_is_wide(n, group) == (n > 2 * group) and shim.mf_header_slots(n, group) == parent_slots_of(n, group) for n in range(1, 8193))
+    assert [n for n in range(1, 8193) if shim.mf_header_slots(n, 1) != parent_slots_of(n, 1)] == [3]
+
+
+def test_the_parents_rule_overran_a_full_mini_batch():
+    """the restated parent rule on the same two properties: it fails the per-run bound at (1, 3) only, and e.g. FunkSVD's mini-batch of 3
+    samples with one item in all of them (runs 3, 1, 1, 1: 6 incidences) needs 7 slots"""
+    assert [(g, n) for g in SLOT_GROUPS for n in range(1, 8193) if parent_slots_of(n, g) > n] == [(1, 3)]
+    assert sum(parent_slots_of(n, 1) for n in (3, 1, 1, 1)) == 7 and sum(slots_of(n, 1) for n in (3, 1, 1, 1)) == 4
+
+
 def test_general_schedule_numbers(recorded):
     seen = set()
     for (s, nb), (batch_bits, end_bit, fits, by_rank) in zip(GENERAL_TABLE, recorded["general/result"].tolist()):
