@@ -590,6 +590,19 @@ int mi355rec_scorer_create(mi355rec_scorer_t *out, int32_t n_users, int32_t n_it
 /* New factor values of the same shapes (after more training epochs). */
 int mi355rec_scorer_update(mi355rec_scorer_t h, const float *U, const float *V, const float *user_bias, const float *item_bias,
                            float global_bias);
+/* The model of an MF training handle into the scorer, device to device.  Replaces mi355rec_mf_get_factors[_f64], the host's float64 ->
+ * float32 pass and mi355rec_scorer_update: U, V (and, when the scorer has biases, user_bias, item_bias and global_bias) end bit for
+ * bit as mi355rec_scorer_update leaves them for float32(what the getters return) -- the rows of the current parity buffers,
+ * rounded to nearest.  n_users, n_items, n_factors and use_bias of the two handles must agree (MI355REC_E_INVALID, naming the
+ * mismatch); an ASY_SVD handle is MI355REC_E_UNSUPPORTED (its user rows are item-sized, the user factors are estimated on the
+ * host); a refused call leaves the scorer's model as it was.  The copy is queued behind the training handle's own work, after the
+ * scorer's stream has drained, and has completed when the call returns.  get_stats of the scorer afterwards: call_ms = kernel_ms =
+ * the copy kernels, algorithmic_bytes = bytes read + written. */
+int mi355rec_scorer_update_from_mf(mi355rec_scorer_t scorer, mi355rec_mf_t mf);
+/* The same from an IALS handle: replaces mi355rec_ials_get_factors, the host's float64 -> float32 pass and mi355rec_scorer_update.
+ * U, V <- float32, rounded to nearest, of the two float64 matrices behind mi355rec_ials_device_factors; the scorer must have the
+ * handle's n_users, n_items, n_factors and no biases. */
+int mi355rec_scorer_update_from_ials(mi355rec_scorer_t scorer, mi355rec_ials_t ials);
 /* For every user of the batch: scores = U[u] . V^T (+ biases); items with item_allowed[j] == 0 (nullable mask) and, when
  * remove_seen, the user's seen items become -inf; ranked[(row) * cutoff ...] = the cutoff best items in descending score
  * order, -1 padded where fewer finite scores exist.  scores (nullable, n x n_items) receives the filtered score matrix. */

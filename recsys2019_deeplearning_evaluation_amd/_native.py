@@ -193,6 +193,8 @@ SIGNATURES = {
     "mi355rec_ease_destroy": (None, [_vp]),
     "mi355rec_scorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _vp, _vp]),
     "mi355rec_scorer_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32]),
+    "mi355rec_scorer_update_from_mf": (C.c_int, [_vp, _vp]),
+    "mi355rec_scorer_update_from_ials": (C.c_int, [_vp, _vp]),
     "mi355rec_scorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mi355rec_scorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mi355rec_scorer_score_capacity": (C.c_int, [_vp, C.POINTER(_i64)]),

@@ -16,6 +16,7 @@
 // ials_diag.cuh); every host decision -- knobs, tile counts and kernel instances, buffer sizes, work items, batches -- is a function
 // of ials_plan.h, which builds and is tested without a GPU.
 #include "common.h"
+#include "score.h"
 #include "ials_solve.cuh"
 
 #include <cstdint>
@@ -414,6 +415,20 @@ extern "C" int mi355rec_ials_get_factors(mi355rec_ials_t h, double *U, double *V
         if (U) h->U.download(U, (size_t)h->n_users * h->k, h->stream);
         if (V) h->V.download(V, (size_t)h->n_items * h->k, h->stream);
         MI_HIP(hipStreamSynchronize(h->stream));
+    });
+}
+
+// (the conversion kernel is handoff.hip's: this file's device code is the epoch's alone)
+extern "C" int mi355rec_scorer_update_from_ials(mi355rec_scorer_t scorer, mi355rec_ials_t h) {
+    return guarded([&] {
+        MI_REQUIRE(scorer && h, "NULL handle");
+        hand_off_check(scorer, "IALS", h->n_users, h->n_items, h->k, 0);
+        ensure_device();
+        const size_t nu = (size_t)h->n_users * h->k, ni = (size_t)h->n_items * h->k;
+        hand_off_begin(scorer, h->stream);
+        f64_to_f32_enqueue(h->U.ptr, scorer->U.ptr, nu, h->stream);
+        f64_to_f32_enqueue(h->V.ptr, scorer->V.ptr, ni, h->stream);
+        hand_off_end(scorer, h->stream, 12.0 * (double)(nu + ni), 2);
     });
 }
 

@@ -37,6 +37,7 @@
 // to O(lr); outputs are float32 either way.
 // There is no dense contraction here, hence no MFMA.
 #include "common.h"
+#include "score.h"
 #include "sampling.cuh"
 #include "wave.cuh"
 
@@ -715,6 +716,38 @@ void get_factors_typed(mi355rec_mf *h, O *U, O *V, O *bu, O *bi, O *mu) {
     }
 }
 
+// mi355rec_scorer_update_from_mf: get_factors_typed<T, float> with the scorer's buffers in the place of `stage` and the host -- the
+// same kernel instances, so the scorer ends with float32(what the getters return), bit for bit
+template <class T>
+void scorer_update_typed(mi355rec_mf *h, mi355rec_scorer *sc) {
+    hipStream_t s = h->stream;
+    MfParams<T> p{};
+    fill_params(h, p);
+    const bool bias = sc->use_bias != 0;
+    if (bias && h->stage.count < 1) h->stage.alloc(1);
+    const unsigned char *par_u = h->par.ptr, *par_v = h->par.ptr + h->n_users;
+    int launches = 0;
+    auto gather = [&](const T *b0, const T *b1, const unsigned char *par, size_t rows, int k, float *out) {
+        hipLaunchKernelGGL((mf_gather_rows_kernel<T, float>), dim3(div_up((long long)rows * k, 256)), dim3(256), 0, s, b0, b1, par,
+                           (long long)rows, k, out);
+        ++launches;
+    };
+    hand_off_begin(sc, s);
+    gather(p.U0, p.U1, par_u, h->n_users, h->k, sc->U.ptr);
+    gather(p.V0, p.V1, par_v, h->n_items, h->k, sc->V.ptr);
+    float mu = 0.f;
+    if (bias) {
+        gather(p.bu0, p.bu1, par_u, h->n_users, 1, sc->bu.ptr);
+        gather(p.bi0, p.bi1, par_v, h->n_items, 1, sc->bi.ptr);
+        hipLaunchKernelGGL((mf_final_mu_kernel<T, float>), dim3(1), dim3(64), 0, s, p, h->stage.ptr);
+        ++launches;
+        MI_HIP(hipMemcpyAsync(&mu, h->stage.ptr, sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    const double cells = ((double)h->n_users + h->n_items) * (h->k + (bias ? 1 : 0));
+    hand_off_end(sc, s, cells * (sizeof(T) + sizeof(float)) + (double)h->n_users + h->n_items, launches);
+    if (bias) sc->mu = mu;
+}
+
 }  // namespace
 
 extern "C" int mi355rec_mf_create(mi355rec_mf_t *out, const mi355rec_mf_config *cfg, int32_t n_users, int32_t n_items,
@@ -1305,6 +1338,19 @@ extern "C" int mi355rec_mf_get_factors_f64(mi355rec_mf_t h, double *U, double *V
         MI_REQUIRE(h, "NULL handle");
         ensure_device();
         if (h->f64) get_factors_typed<double, double>(h, U, V, bu, bi, mu); else get_factors_typed<float, double>(h, U, V, bu, bi, mu);
+    });
+}
+
+extern "C" int mi355rec_scorer_update_from_mf(mi355rec_scorer_t scorer, mi355rec_mf_t h) {
+    return guarded([&] {
+        MI_REQUIRE(scorer && h, "NULL handle");
+        if (h->cfg.algorithm == MI355REC_MF_ASY_SVD)
+            fail(MI355REC_E_UNSUPPORTED, "an ASY_SVD handle cannot be handed to a scorer: its user rows are item-sized and the user "
+                                         "factors are estimated on the host");
+        hand_off_check(scorer, "MF", h->n_users, h->n_items, h->k, h->cfg.use_bias);
+        ensure_device();
+        ReleaseScope scope(h->stream);
+        if (h->f64) scorer_update_typed<double>(h, scorer); else scorer_update_typed<float>(h, scorer);
     });
 }
 

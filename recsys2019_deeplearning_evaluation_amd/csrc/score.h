@@ -154,4 +154,15 @@ Ranking spexact_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int 
 // f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
 void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);
 
+// handoff.hip: what mi355rec_scorer_update_from_mf (mf.hip) and mi355rec_scorer_update_from_ials (ials.hip) share.
+// out[i] = (float)in[i], round to nearest, for i < n; queued on `s`
+void f64_to_f32_enqueue(const double *in, float *out, size_t n, hipStream_t s);
+// the refusals: the shape and the biases of the `source` handle ("MF", "IALS") against the scorer's (MI355REC_E_INVALID)
+void hand_off_check(const mi355rec_scorer *sc, const char *source, int n_users, int n_items, int k, int use_bias);
+// Around the copy kernels, which the caller queues on the training handle's stream `source`, behind that handle's own work: begin
+// drains the scorer's stream first (nothing reads the old model any more) and starts the scorer's call_timer on `source`; end stops
+// it, waits for `source` -- neither handle's later work can race the copy -- and fills the scorer's stats.
+void hand_off_begin(mi355rec_scorer *sc, hipStream_t source);
+void hand_off_end(mi355rec_scorer *sc, hipStream_t source, double bytes, int launches);
+
 }  // namespace mi355rec

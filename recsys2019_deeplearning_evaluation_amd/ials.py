@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _native as N
 from .recommender_base import (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping, check_matrix)
-from .scoring import GpuScoringMixin
+from .scoring import HandOffScoringMixin, ValidationHandOff
 
 
 class IALS_MI355X_Epoch(N.Handle):
@@ -62,8 +62,9 @@ class IALS_MI355X_Epoch(N.Handle):
         return a.value, b.value
 
 
-class _IALSLogic:
-    """Drop-in for the reference IALSRecommender with _run_epoch on the GPU (a mixin without bases, see matrix_factorization.py)."""
+class _IALSLogic(ValidationHandOff):
+    """Drop-in for the reference IALSRecommender with _run_epoch on the GPU (a mixin without recommender bases, see
+    matrix_factorization.py).  `validation_hand_off` ("host" / "device"): scoring.ValidationHandOff."""
     RECOMMENDER_NAME = "IALSRecommender"
     AVAILABLE_CONFIDENCE_SCALING = ["linear", "log"]
 
@@ -72,6 +73,7 @@ class _IALSLogic:
         if confidence_scaling not in self.AVAILABLE_CONFIDENCE_SCALING:
             raise ValueError("Value for 'confidence_scaling' not recognized. Acceptable values are {}, provided was '{}'".format(
                 self.AVAILABLE_CONFIDENCE_SCALING, confidence_scaling))
+        self._begin_hand_off()                  # (an unknown mode is refused before the device is touched)
         self.num_factors = num_factors
         self.alpha = alpha
         self.epsilon = epsilon
@@ -82,6 +84,7 @@ class _IALSLogic:
         self.epoch_kernel = IALS_MI355X_Epoch(self.C, num_factors, reg, self.ITEM_factors, self.USER_factors)
         self._update_best_model()
         self._train_with_early_stopping(epochs, algorithm_name=self.RECOMMENDER_NAME, **earlystopping_kwargs)
+        self._end_hand_off()
         self.USER_factors = self.USER_factors_best
         self.ITEM_factors = self.ITEM_factors_best
         self.epoch_kernel.close()
@@ -95,13 +98,21 @@ class _IALSLogic:
         Cm.data = Cm.data.astype(np.float32)
         self.C = Cm
 
+    def _download_model(self):
+        self.USER_factors, self.ITEM_factors = self.epoch_kernel.get_factors()
+
     def _prepare_model_for_validation(self):
+        if self._hand_off_on_device():
+            return self._hand_off_model()
         self.USER_factors, self.ITEM_factors = self.epoch_kernel.get_factors()
         invalidate = getattr(self, "invalidate_scorer", None)         # (the device scorer of the scoring mixin, if the class has one)
         if invalidate is not None:
             invalidate()
 
     def _update_best_model(self):
+        if self._host_model_stale:              # device mode: the training handle has not advanced since the validation
+            self.USER_factors_best, self.ITEM_factors_best = self.epoch_kernel.get_factors()
+            return
         self.USER_factors_best = self.USER_factors.copy()
         self.ITEM_factors_best = self.ITEM_factors.copy()
 
@@ -109,5 +120,5 @@ class _IALSLogic:
         self.epoch_kernel.run_epochs(1)
 
 
-class IALSRecommender(_IALSLogic, GpuScoringMixin, BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping):
+class IALSRecommender(_IALSLogic, HandOffScoringMixin, BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping):
     pass

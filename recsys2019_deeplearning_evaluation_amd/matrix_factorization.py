@@ -21,7 +21,7 @@ import numpy as np
 from . import _native as N
 from .recommender_base import (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping,
                                check_matrix)
-from .scoring import GpuScoringMixin
+from .scoring import HandOffScoringMixin, ValidationHandOff
 
 
 class MatrixFactorization_MI355X_Epoch(N.Handle):
@@ -192,10 +192,10 @@ class MatrixFactorization_MI355X_Group(N.Handle):
         self._call("set_profiling", int(max_timed_launches))
 
 
-class _MatrixFactorizationLogic:
+class _MatrixFactorizationLogic(ValidationHandOff):
     """fit() / early-stopping hooks of MatrixFactorization_Cython.py:20-170 over the device epoch object.  A mixin without
-    bases: composed below with this package's re-provided recommender bases, and by reference_binding.bind() with the
-    reference's own Base classes."""
+    recommender bases: composed below with this package's re-provided recommender bases, and by reference_binding.bind() with the
+    reference's own Base classes.  `validation_hand_off` ("host" / "device"): scoring.ValidationHandOff."""
     RECOMMENDER_NAME = "MatrixFactorization_MI355X_Recommender"
 
     def __init__(self, URM_train, verbose=True, algorithm_name="MF_BPR"):
@@ -208,6 +208,7 @@ class _MatrixFactorizationLogic:
             use_bias=True, sgd_mode="sgd", negative_interactions_quota=0.0, init_mean=0.0, init_std_dev=0.1,
             user_reg=0.0, item_reg=0.0, bias_reg=0.0, positive_reg=0.0, negative_reg=0.0, random_seed=None,
             **earlystopping_kwargs):
+        hand_off = self._begin_hand_off()       # (an unknown mode, or "device" where it cannot be, is refused before the device is touched)
         self.num_factors = num_factors
         self.use_bias = use_bias
         self.sgd_mode = sgd_mode
@@ -234,9 +235,13 @@ class _MatrixFactorizationLogic:
                     "MatrixFactorization_Cython: URM_train_positive is empty, positive threshold is too high"
             self.epoch_kernel = MatrixFactorization_MI355X_Epoch(
                 URM_positive, positive_reg=positive_reg, negative_reg=negative_reg, **common)
-        self._prepare_model_for_validation()
+        if hand_off:
+            self._download_model()              # the one download a fit makes without a new best: the initial model
+        else:
+            self._prepare_model_for_validation()
         self._update_best_model()
         self._train_with_early_stopping(epochs, algorithm_name=self.algorithm_name, **earlystopping_kwargs)
+        self._end_hand_off()
         self.USER_factors = self.USER_factors_best
         self.ITEM_factors = self.ITEM_factors_best
         if self.use_bias:
@@ -251,7 +256,15 @@ class _MatrixFactorizationLogic:
         if invalidate is not None:
             invalidate()
 
-    def _prepare_model_for_validation(self):     # the only device -> host copy of the training loop
+    def _download_model(self):
+        """Device mode's download: the host attributes from the training handle, in one call -- the arrays host mode's getters return."""
+        self.USER_factors, self.ITEM_factors, bu, bi, mu = self.epoch_kernel._download(self.use_bias)
+        if self.use_bias:
+            self.USER_bias, self.ITEM_bias, self.GLOBAL_bias = bu, bi, np.array(mu[0])
+
+    def _prepare_model_for_validation(self):     # host mode: the only device -> host copy of the training loop
+        if self._hand_off_on_device():
+            return self._hand_off_model()
         self.USER_factors, self.ITEM_factors = self.epoch_kernel.get_factors()
         self._forget_device_scorer()
         if self.use_bias:
@@ -260,6 +273,12 @@ class _MatrixFactorizationLogic:
             self.GLOBAL_bias = self.epoch_kernel.get_GLOBAL_bias()
 
     def _update_best_model(self):
+        if self._host_model_stale:
+            # device mode: the training handle has not advanced since the validation, so these are the arrays host mode copies here
+            self.USER_factors_best, self.ITEM_factors_best, bu, bi, mu = self.epoch_kernel._download(self.use_bias)
+            if self.use_bias:
+                self.USER_bias_best, self.ITEM_bias_best, self.GLOBAL_bias_best = bu, bi, np.array(mu[0])
+            return
         self.USER_factors_best = self.USER_factors.copy()
         self.ITEM_factors_best = self.ITEM_factors.copy()
         if self.use_bias:
@@ -299,6 +318,7 @@ class _AsySVDLogic(_MatrixFactorizationLogic):
     """Drop-in for MatrixFactorization_AsySVD_Cython (MatrixFactorization_Cython.py:219): two item-sized factor matrices;
     a user's factors are the sum of the Y rows of its profile divided by sqrt(profile length)."""
     RECOMMENDER_NAME = "MatrixFactorization_AsySVD_MI355X_Recommender"
+    _HAND_OFF_SUPPORTED = False       # validation_hand_off = "device" is a ValueError at fit: USER_factors are estimated on the host
 
     def __init__(self, *pos_args, **key_args):
         super(_AsySVDLogic, self).__init__(*pos_args, algorithm_name="ASY_SVD", **key_args)
@@ -340,7 +360,7 @@ class _AsySVDLogic(_MatrixFactorizationLogic):
         return USER_factors
 
 
-_BASES = (GpuScoringMixin, BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
+_BASES = (HandOffScoringMixin, BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
 
 
 class MatrixFactorization_BPR_MI355X(_BPRLogic, *_BASES):

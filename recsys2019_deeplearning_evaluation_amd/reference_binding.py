@@ -35,7 +35,7 @@ from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
 from .nmf import _NMFLogic
 from .non_personalized import _GlobalEffectsLogic, _RandomLogic, _TopPopLogic
 from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
-from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin
+from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin, HandOffScoringMixin
 from .slim_bpr import _SLIMLogic
 from .slim_elasticnet import _SLIMElasticNetLogic
 
@@ -49,7 +49,8 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
     (TopPop, GlobalEffects, Random) derive from `Base.BaseRecommender` itself: they are rebuilt when BaseRecommender is given."""
     mf_score = (GpuScoringMixin,) if device_scoring else ()
     sim_score = (GpuSimilarityScoringMixin,) if device_scoring else ()
-    mf = mf_score + (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
+    # (the recommenders that train with validations: the scoring mixin that also serves validation_hand_off = "device")
+    mf = ((HandOffScoringMixin,) if device_scoring else ()) + (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
     table = {
         "MatrixFactorization_BPR_MI355X": (_BPRLogic,) + mf,
         "MatrixFactorization_FunkSVD_MI355X": (_FunkSVDLogic,) + mf,

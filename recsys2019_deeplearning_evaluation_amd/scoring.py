@@ -77,6 +77,24 @@ class MI355XScorer(_Scorer):
         bi = N.as_f32(ITEM_bias) if self.use_bias else None
         self._call("update", N.ptr(U), N.ptr(V), N.ptr(bu), N.ptr(bi), float(np.asarray(GLOBAL_bias)))
 
+    def update_from(self, epoch_object):
+        """The model a training handle holds in HBM -- a MatrixFactorization_MI355X_Epoch (BPR, FunkSVD) or an IALS_MI355X_Epoch -- into
+        the scorer, device to device: the values `update(*np.float32(get_factors()), ...biases)` would upload, bit for bit, without
+        the download, the host's float64 -> float32 pass and the upload.  ValueError when the shapes or the biases of the two differ
+        or the handle is closed, NotImplementedError for an AsySVD handle; the scorer then keeps the model it had."""
+        from .ials import IALS_MI355X_Epoch
+        from .matrix_factorization import MatrixFactorization_MI355X_Epoch
+        if isinstance(epoch_object, MatrixFactorization_MI355X_Epoch):
+            entry = "update_from_mf"
+        elif isinstance(epoch_object, IALS_MI355X_Epoch):
+            entry = "update_from_ials"
+        else:
+            raise TypeError("update_from takes a MatrixFactorization_MI355X_Epoch or an IALS_MI355X_Epoch, got {}".format(
+                type(epoch_object).__name__))
+        if not epoch_object._h:
+            raise ValueError("%s is closed" % type(epoch_object).__name__)
+        self._call(entry, epoch_object._h)
+
     def score_capacity(self):
         """Cells of the device buffer for (users x n_items) score rows: 0 until a full-row recommend() has needed it; the candidate
         path never touches it."""
@@ -210,6 +228,102 @@ class GpuScoringMixin(_ScoringMixin):
 
     def device_scorer(self):
         return self._get_scorer()
+
+
+class ValidationHandOff:
+    """How an early-stopping fit hands the model to its validations: a mixin without bases for the logic classes of the recommenders
+    whose training handle keeps the model in HBM (BPR-MF, FunkSVD, IALS; AsySVD carries the attribute and refuses "device").
+
+    `validation_hand_off` (class or object attribute) is "host", the default -- every validation downloads the model into
+    USER_factors / ITEM_factors[/biases] and the scorer uploads it again, as before -- or "device": the scorer is filled from the
+    training handle device to device (`MI355XScorer.update_from`) and the host attributes are only marked stale.  While they are,
+    `device_scorer()` returns that scorer as it is, without a fingerprint or an upload, whoever asks (recommend(), either device
+    evaluator), and `_sync_host_model()` downloads the model for whatever reads the attributes on the host (_compute_item_score,
+    save_model): the scorer's half, HandOffScoringMixin below, which device mode needs.  A new best model is downloaded from the
+    training handle, which has not advanced since the validation.  At the end of fit the attributes are the best model, the flags
+    are cleared and the scorer cache is back to its identity + fingerprint rule.
+
+    A logic class provides `_download_model()`: the host attributes from `self.epoch_kernel`."""
+    VALIDATION_HAND_OFF_MODES = ("host", "device")
+    validation_hand_off = "host"
+    _HAND_OFF_SUPPORTED = True      # (AsySVD: its user factors are estimated on the host from item-sized rows)
+    _host_model_stale = False       # the host attributes are older than the model the scorer holds
+    _scorer_current = False         # the scorer holds the training handle's model: device_scorer() returns it as it is
+
+    def _hand_off_on_device(self):
+        """True in device mode; ValueError for an unknown mode or a class that cannot hand off -- before the device is touched."""
+        mode = self.validation_hand_off
+        if mode not in self.VALIDATION_HAND_OFF_MODES:
+            raise ValueError("{}: validation_hand_off must be one of {}, got {!r}".format(type(self).__name__,
+                                                                                        self.VALIDATION_HAND_OFF_MODES, mode))
+        if mode == "host":
+            return False
+        if not self._HAND_OFF_SUPPORTED:
+            raise ValueError("{}: validation_hand_off = 'device' is not supported: the user factors of this model are estimated on "
+                             "the host".format(type(self).__name__))
+        if not isinstance(self, HandOffScoringMixin):
+            raise ValueError("{}: validation_hand_off = 'device' needs the device scorer (HandOffScoringMixin)".format(type(self).__name__))
+        return True
+
+    def _begin_hand_off(self):
+        """First thing in fit(): the mode is checked, and a device-mode fit starts without a scorer, as a host-mode one does."""
+        self._end_hand_off()
+        device = self._hand_off_on_device()
+        if device:
+            self.invalidate_scorer()
+        return device
+
+    def _end_hand_off(self):
+        self._host_model_stale = False
+        self._scorer_current = False
+
+    def _download_model(self):
+        raise NotImplementedError("{}: _download_model".format(type(self).__name__))
+
+
+class HandOffScoringMixin(GpuScoringMixin):
+    """GpuScoringMixin for the recommenders with a ValidationHandOff logic class: the scorer's half of device mode.  With the flags
+    clear -- host mode, and device mode outside a fit -- every method is its parent's."""
+    _host_model_stale = False
+    _scorer_current = False
+
+    def _hand_off_model(self):
+        """_prepare_model_for_validation of device mode.  The first time in a fit the scorer is built from the host attributes as
+        they stand (which uploads the seen CSR, too); from then on it is only filled from the training handle."""
+        if not self._scorer_current:
+            self._get_scorer()
+        self._scorer.update_from(self.epoch_kernel)
+        self._host_model_stale = True
+        self._scorer_current = True
+
+    def _sync_host_model(self):
+        """The host attributes <- the model that is being validated, if they are stale; nothing is downloaded otherwise."""
+        if self._host_model_stale:
+            self._download_model()
+            self._host_model_stale = False
+
+    def device_scorer(self):
+        if self._scorer_current:
+            if self._scorer is not None and self._scorer_src["urm"] is self.URM_train:
+                return self._scorer
+            self._sync_host_model()             # (URM_train was replaced mid-fit: back to the cache rule, which builds a new scorer)
+            self._scorer_current = False
+        return super(HandOffScoringMixin, self).device_scorer()
+
+    def invalidate_scorer(self):
+        if self._host_model_stale and getattr(getattr(self, "epoch_kernel", None), "_h", None):
+            self._sync_host_model()             # (the scorer held the only copy of the validated model outside the training handle)
+        self._host_model_stale = False
+        self._scorer_current = False
+        super(HandOffScoringMixin, self).invalidate_scorer()
+
+    def _compute_item_score(self, user_id_array, items_to_compute=None):
+        self._sync_host_model()
+        return super(HandOffScoringMixin, self)._compute_item_score(user_id_array, items_to_compute=items_to_compute)
+
+    def save_model(self, folder_path, file_name=None):
+        self._sync_host_model()
+        return super(HandOffScoringMixin, self).save_model(folder_path, file_name=file_name)
 
 
 class MI355XSparseScorer(_Scorer):
