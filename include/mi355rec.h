@@ -651,6 +651,29 @@ int mi355rec_spscorer_recommend_candidates(mi355rec_spscorer_t h, const int32_t 
  * get_stats after an exact recommend: kernel_ms = call_ms = the exact scoring kernel (recommend_candidates: that kernel and the
  * candidates' gather + ranking). */
 int mi355rec_spscorer_set_exact(mi355rec_spscorer_t h, int32_t exact);
+/* Replaces B by another host CSR of the same n_mid x n_items, with any number of cells; A and the seen CSR stay where they are.
+ * Afterwards the scorer answers mi355rec_spscorer_recommend[_candidates] and mi355rec_eval_add_spscorer[_candidates] exactly as one
+ * freshly created with that B would, in either mode; in exact mode the table of the mode is rebuilt for the new B.
+ * MI355REC_E_INVALID, checked on the host before anything is uploaded, the message naming the first offending row: a NULL argument,
+ * row pointers that do not start at 0 or that decrease, a column id outside [0, n_items) and -- in exact mode -- a row whose ids are
+ * not strictly ascending.  A refused call leaves the scorer's B and mode as they were and the handle usable: the new B is written
+ * into spare buffers and swapped in once it has been accepted.  The scorer's stream is drained first (an evaluator may still have
+ * lists queued that read the old B).  get_stats: call_ms = kernel_ms = the copies (and the exact pass), algorithmic_bytes = what
+ * they read and wrote on the device. */
+int mi355rec_spscorer_update_b(mi355rec_spscorer_t h, const int32_t *b_indptr, const int32_t *b_indices, const float *b_data);
+/* Downloads B as the scorer holds it: indptr[n_mid + 1], and *nnz entries of indices and data.  With indices == NULL (and
+ * data == NULL) only indptr and *nnz come back: call once for the size, then again with arrays of that size. */
+int mi355rec_spscorer_get_b(mi355rec_spscorer_t h, int32_t *indptr, int32_t *indices, float *data, int64_t *nnz);
+/* B <- the CSR that mi355rec_slim_get_W_csr(slim, topK, ...) would return -- indptr, indices and data bit for bit -- device to
+ * device: it replaces that download, the host's assembly of the matrix and the creation of a new scorer with A, the seen CSR and W
+ * uploaded again.  The SLIM handle is only read.  Ordering: the scorer's stream is drained; the build of W and the copy are queued
+ * on the SLIM handle's stream behind its own work; the call returns after that stream has been waited for.  Refusals, which leave
+ * the scorer as it was: MI355REC_E_INVALID for a NULL handle, for a SLIM handle whose n_items is not both n_mid and n_items of the
+ * scorer (a user-based scorer; the message names the values) and for topK < 1; MI355REC_E_UNSUPPORTED for a handle created with
+ * train_with_sparse_weights (reading its model prunes it), for n_items > 65 535 and for a topK beyond the in-LDS selection, as
+ * mi355rec_slim_get_W_csr.  In exact mode the table is rebuilt.  get_stats of the scorer: call_ms = kernel_ms = the device work of
+ * the call, algorithmic_bytes = the weight store read once + W read and written (+ the exact pass). */
+int mi355rec_spscorer_update_from_slim(mi355rec_spscorer_t h, mi355rec_slim_t slim, int32_t topK);
 int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats);
 void mi355rec_spscorer_destroy(mi355rec_spscorer_t h);
 

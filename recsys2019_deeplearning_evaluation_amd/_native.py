@@ -204,6 +204,9 @@ SIGNATURES = {
     "mi355rec_spscorer_recommend": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "mi355rec_spscorer_recommend_candidates": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "mi355rec_spscorer_set_exact": (C.c_int, [_vp, _i32]),
+    "mi355rec_spscorer_update_b": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mi355rec_spscorer_get_b": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "mi355rec_spscorer_update_from_slim": (C.c_int, [_vp, _vp, _i32]),
     "mi355rec_spscorer_get_stats":(C.c_int, [_vp, C.POINTER(Stats)]),
     "mi355rec_spscorer_destroy": (None, [_vp]),
     "mi355rec_dscorer_create": (C.c_int, [C.POINTER(_vp), _i32, _i32, _i32] + [_vp] * 6),

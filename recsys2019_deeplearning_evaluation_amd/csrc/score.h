@@ -91,6 +91,11 @@ struct mi355rec_spscorer final : mi355rec::ScorerHandle {    // `timer`: the sco
     mi355rec::DeviceBuffer<int> a_ptr, a_idx, b_ptr, b_idx;
     mi355rec::DeviceBuffer<int> cuts;               // exact mode: where every row of B crosses into each slice of a score row
     mi355rec::DeviceBuffer<float> a_val, b_val;
+    // What a new B is written into (update_b, update_from_slim): swapped with b_ptr / b_idx / b_val once the new B has been accepted,
+    // never before -- so they then hold the B that was replaced, and serve the next call.  After the first replacement b_idx and
+    // b_val may be larger than B: nnz_b, not their count, says how many cells B has.
+    mi355rec::DeviceBuffer<int> spare_ptr, spare_idx;
+    mi355rec::DeviceBuffer<float> spare_val;
     double nnz_a = 0, nnz_b = 0;
 
     mi355rec::Ranking enqueue(const int *users, int n, int cutoff, int remove_seen, const unsigned char *allowed, bool keep_scores) override;
@@ -150,6 +155,13 @@ Ranking spexact_enqueue(mi355rec_spscorer_t h, const int *users, int n, int cuto
                         bool keep_scores);
 Ranking spexact_enqueue_candidates(mi355rec_spscorer_t h, const int *users, int n, int cutoff, int remove_seen,
                                    const unsigned char *allowed, const CandidateRows &rows);
+// spexact.hip: the pass of exact mode over a B on the device (b_ptr, b_idx: the live buffers, or the spare ones of a B that is about to
+// be swapped in), queued on `s`: every row's ids strictly ascending inside [0, n_items) -- MI355REC_E_INVALID naming the first row that
+// is not -- and, where `cuts` is given, the table of that B into it.  Returns with `s` drained.  The table is a function of B:
+// whoever replaces B on an exact scorer calls this and swaps the table in together with B.
+void spexact_check_and_cut(mi355rec_spscorer_t h, hipStream_t s, const int *b_ptr, const int *b_idx, DeviceBuffer<int> *cuts);
+// cells of that table (0 when the scorer is not in exact mode): for the byte accounting of the calls that replace B
+size_t spexact_table_cells(const mi355rec_spscorer *h);
 // C[b][j] = A[rows[b]] . Bt[j] for b < n, j < m (A: rows of k floats, Bt: m x k, C: n x m, all row-major on the device): the scorer's
 // f32 MFMA GEMM without biases, queued on `s`.  n <= 128 * 65535.
 void gemm_rows_enqueue(const float *A, const int *rows, int n, int k, const float *Bt, int m, float *C, hipStream_t s);
@@ -164,5 +176,24 @@ void hand_off_check(const mi355rec_scorer *sc, const char *source, int n_users, 
 // it, waits for `source` -- neither handle's later work can race the copy -- and fills the scorer's stats.
 void hand_off_begin(mi355rec_scorer *sc, hipStream_t source);
 void hand_off_end(mi355rec_scorer *sc, hipStream_t source, double bytes, int launches);
+
+// handoff.hip: a CSR that is already on the device (n_mid + 1 row pointers, at most `max_cells` ids and values; n_mid x n_items) becomes
+// the sparse scorer's B.  What mi355rec_spscorer_update_from_slim (slim.hip) is made of, and what the next device-resident similarity
+// model goes through:
+//   begin   drains the scorer's stream (lists an evaluator queued there still read the old B) and starts the scorer's `timer` on
+//           `source`, the stream of the handle that owns the CSR; the caller then queues whatever builds the CSR on `source`;
+//   adopt   queues csr_adopt_kernel on `source` -- the CSR is copied into the spare buffers and checked in the same pass -- and waits.
+//           A CSR that is not canonical (pointers from 0 upwards within max_cells, ids strictly ascending inside [0, n_items)) is a
+//           bug of whoever built it: MI355REC_E_HIP naming the row, the scorer as it was.  In exact mode the table is rebuilt.  Then
+//           the buffers are swapped, nnz_b follows, and the stats are call_ms = kernel_ms = begin .. here on `source`,
+//           algorithmic_bytes = build_bytes (what building the CSR read) + the adopt pass's read and write + the exact table's,
+//           n_launches = build_launches + the ones made here.
+void spscorer_adopt_begin(mi355rec_spscorer *sc, hipStream_t source);
+void spscorer_adopt(mi355rec_spscorer *sc, hipStream_t source, const int *indptr, const int *indices, const float *data, size_t max_cells,
+                    double build_bytes, int build_launches);
+// score.hip: room for a B of `cells` cells in the spare buffers (spscorer_plan.h's growth rule); the caller has drained h->stream
+void spscorer_reserve_spare(mi355rec_spscorer *h, size_t cells);
+// score.hip: the spare buffers, holding an accepted B of nnz cells (and `cuts`, its table, on an exact scorer), become the live ones
+void spscorer_swap_in(mi355rec_spscorer *h, size_t nnz, DeviceBuffer<int> &cuts);
 
 }  // namespace mi355rec

@@ -18,6 +18,7 @@
 //                      row, the first `cutoff` finite entries are the ranking.
 #include "common.h"
 #include "score.h"
+#include "spscorer_plan.h"
 #include "topk.cuh"
 
 #include <rocprim/rocprim.hpp>
@@ -605,6 +606,85 @@ void mi355rec_spscorer::fill_recommend_stats(const int32_t *, int) { stats.kerne
 extern "C" int mi355rec_spscorer_recommend(mi355rec_spscorer_t h, const int32_t *user_ids, int32_t n, int32_t cutoff,
                                            int32_t remove_seen, const uint8_t *item_allowed, int32_t *ranked, float *scores) {
     return guarded([&] { recommend(h, user_ids, n, cutoff, remove_seen, item_allowed, ranked, scores); });
+}
+
+// ---- replacing B (host code only) -----------------------------------------------------------------------------
+namespace mi355rec {
+
+void spscorer_reserve_spare(mi355rec_spscorer *h, size_t cells) {
+    if (h->spare_ptr.count != (size_t)h->n_mid + 1) h->spare_ptr.alloc((size_t)h->n_mid + 1);
+    const size_t room = spscorer_plan::spare_cells(h->spare_idx.count, cells);
+    if (room != h->spare_idx.count) {
+        h->spare_idx.alloc(room);
+        h->spare_val.alloc(room);
+    }
+}
+
+void spscorer_swap_in(mi355rec_spscorer *h, size_t nnz, DeviceBuffer<int> &cuts) {
+    h->b_ptr.swap(h->spare_ptr);
+    h->b_idx.swap(h->spare_idx);
+    h->b_val.swap(h->spare_val);
+    h->nnz_b = (double)nnz;
+    if (h->exact) h->cuts.swap(cuts);
+    else h->cuts.release();         // (the table was the old B's: the next switch-on builds the new one)
+}
+
+}  // namespace mi355rec
+
+extern "C" int mi355rec_spscorer_update_b(mi355rec_spscorer_t h, const int32_t *b_indptr, const int32_t *b_indices, const float *b_data) {
+    return guarded([&] {
+        MI_REQUIRE(h && b_indptr && b_indices && b_data, "NULL argument");
+        using spscorer_plan::CsrFinding;
+        const CsrFinding f = spscorer_plan::check_csr(h->n_mid, h->n_items, b_indptr, b_indices, h->exact != 0);
+        MI_REQUIRE(f.kind != CsrFinding::START_NOT_ZERO, "update_b: the row pointers of B start at %lld, not at 0 (row 0)", (long long)f.value);
+        MI_REQUIRE(f.kind != CsrFinding::POINTERS_DECREASE, "update_b: the row pointers of B decrease at row %d (to %lld)", f.row, (long long)f.value);
+        MI_REQUIRE(f.kind != CsrFinding::ID_OUTSIDE, "update_b: row %d of B holds the column id %lld outside [0, %d)", f.row, (long long)f.value, h->n_items);
+        MI_REQUIRE(f.kind != CsrFinding::NOT_ASCENDING, "update_b: exact mode: row %d of B does not hold its column ids strictly ascending (a column "
+                   "twice, or unsorted, at id %lld)", f.row, (long long)f.value);
+        ensure_device();
+        hipStream_t s = h->stream;
+        ReleaseScope scope(s);
+        MI_HIP(hipStreamSynchronize(s));        // lists an evaluator queued on this stream still read the old B
+        const size_t nnz = (size_t)b_indptr[h->n_mid];
+        spscorer_reserve_spare(h, nnz);
+        h->timer.start(s);
+        MI_HIP(hipMemcpyAsync(h->spare_ptr.ptr, b_indptr, sizeof(int) * ((size_t)h->n_mid + 1), hipMemcpyHostToDevice, s));
+        if (nnz) {
+            MI_HIP(hipMemcpyAsync(h->spare_idx.ptr, b_indices, sizeof(int) * nnz, hipMemcpyHostToDevice, s));
+            MI_HIP(hipMemcpyAsync(h->spare_val.ptr, b_data, sizeof(float) * nnz, hipMemcpyHostToDevice, s));
+        }
+        DeviceBuffer<int> cuts;
+        if (h->exact) spexact_check_and_cut(h, s, h->spare_ptr.ptr, h->spare_idx.ptr, &cuts);     // (set_exact's check, on the new B)
+        h->timer.stop(s);
+        MI_HIP(hipStreamSynchronize(s));
+        spscorer_swap_in(h, nnz, cuts);
+        h->stats = mi355rec_stats{};
+        h->stats.call_ms = h->stats.kernel_ms = h->timer.elapsed_ms();
+        h->stats.n_launches = h->stats.n_timed = h->exact ? 2 : 0;
+        h->stats.algorithmic_bytes = spscorer_plan::update_b_bytes(h->n_mid, nnz, spexact_table_cells(h));
+    });
+}
+
+extern "C" int mi355rec_spscorer_get_b(mi355rec_spscorer_t h, int32_t *indptr, int32_t *indices, float *data, int64_t *nnz) {
+    return guarded([&] {
+        MI_REQUIRE(h && indptr && nnz, "NULL argument");
+        MI_REQUIRE((indices == nullptr) == (data == nullptr), "indices and data: both or neither");
+        ensure_device();
+        hipStream_t s = h->stream;
+        const size_t n = (size_t)h->nnz_b;
+        h->timer.start(s);
+        h->b_ptr.download(indptr, (size_t)h->n_mid + 1, s);
+        if (indices && n) {
+            MI_HIP(hipMemcpyAsync(indices, h->b_idx.ptr, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+            MI_HIP(hipMemcpyAsync(data, h->b_val.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+        }
+        h->timer.stop(s);
+        MI_HIP(hipStreamSynchronize(s));
+        *nnz = (int64_t)n;
+        h->stats = mi355rec_stats{};
+        h->stats.call_ms = h->stats.kernel_ms = h->timer.elapsed_ms();
+        h->stats.algorithmic_bytes = spscorer_plan::get_b_bytes(h->n_mid, n, indices != nullptr);
+    });
 }
 
 extern "C" int mi355rec_spscorer_get_stats(mi355rec_spscorer_t h, mi355rec_stats *stats) { return handle_get_stats(h, stats); }

@@ -35,6 +35,7 @@
 // ordered fallback), slim_schedule.cuh (sampler, dependencies of a stream), slim_readout.cuh (get_S, prune / list, W).  Host code
 // that makes no HIP call: slim_plan.h (knobs, grids, segment cuts), slim_gate.h (owner gate, compute-unit lease).
 #include "common.h"
+#include "score.h"
 
 #include "sampling.cuh"
 #include "topk.cuh"
@@ -611,15 +612,31 @@ void run_epochs_typed(mi355rec_slim *h, int n_epochs) {
 template <class T>
 void topk_slabs_on_device(mi355rec_slim *h, int topK, DeviceBuffer<int> &d_idx, DeviceBuffer<float> &d_val);
 
-template <class T>
-void get_w_csr_typed(mi355rec_slim *h, int topK, int *nbr_idx, float *nbr_val, int *indptr, int *indices, float *data, long long *nnz) {
-    MI_REQUIRE(h->n_items <= 65535, "n_items = %d: the device-side column selection packs items into 16 bits", h->n_items);
-    hipStream_t s = h->stream;
+// W = similarityMatrixTopK(get_S(), topK) as it stands in device buffers after build_w_on_device: the canonical CSR is d_indptr
+// [n_items + 1] and the first d_indptr[n_items] entries of d_indices / val2_sorted (each n_items * topK long), rows with strictly
+// ascending columns; d_idx / d_val are the per-row slabs of get_S().  The rest is scratch of the build, alive until the caller lets go.
+struct WBuild {
     DeviceBuffer<int> d_idx, slot, slot_sorted, col_start, d_indptr, d_indices;
     DeviceBuffer<float> d_val, val2, val2_sorted;
     DeviceBuffer<unsigned long long> key, key_sorted;
     DeviceBuffer<unsigned> key2, key2_sorted;
     DeviceBuffer<unsigned char> tmp;
+    size_t n_slots = 0;
+};
+constexpr int W_BUILD_LAUNCHES = 7;     // selection, keys, sort, column starts, keep, sort, CSR
+
+// The first half of mi355rec_slim_get_W_csr, queued on the handle's stream and not waited for: also what
+// mi355rec_spscorer_update_from_slim hands to the sparse scorer.
+template <class T>
+void build_w_on_device(mi355rec_slim *h, int topK, WBuild &w) {
+    MI_REQUIRE(h->n_items <= 65535, "n_items = %d: the device-side column selection packs items into 16 bits", h->n_items);
+    hipStream_t s = h->stream;
+    DeviceBuffer<int> &d_idx = w.d_idx, &slot = w.slot, &slot_sorted = w.slot_sorted, &col_start = w.col_start, &d_indptr = w.d_indptr,
+                      &d_indices = w.d_indices;
+    DeviceBuffer<float> &d_val = w.d_val, &val2 = w.val2, &val2_sorted = w.val2_sorted;
+    DeviceBuffer<unsigned long long> &key = w.key, &key_sorted = w.key_sorted;
+    DeviceBuffer<unsigned> &key2 = w.key2, &key2_sorted = w.key2_sorted;
+    DeviceBuffer<unsigned char> &tmp = w.tmp;
     topk_slabs_on_device<T>(h, topK, d_idx, d_val);
     const size_t n_slots = (size_t)h->n_items * topK;
     MI_REQUIRE(n_slots < (size_t)INT32_MAX, "too many slab entries");
@@ -641,17 +658,37 @@ void get_w_csr_typed(mi355rec_slim *h, int topK, int *nbr_idx, float *nbr_val, i
     hipLaunchKernelGGL(slim_w_csr_kernel, dim3(std::max(grid, (unsigned)((h->n_items + 256) / 256))), dim3(256), 0, s, key2_sorted.ptr, n_slots, h->n_items,
                        d_indptr.ptr, d_indices.ptr);
     MI_HIP(hipGetLastError());
-    d_indptr.download(indptr, (size_t)h->n_items + 1, s);
+    w.n_slots = n_slots;
+}
+
+// ... and the second half: the download
+template <class T>
+void get_w_csr_typed(mi355rec_slim *h, int topK, int *nbr_idx, float *nbr_val, int *indptr, int *indices, float *data, long long *nnz) {
+    hipStream_t s = h->stream;
+    WBuild w;
+    build_w_on_device<T>(h, topK, w);
+    w.d_indptr.download(indptr, (size_t)h->n_items + 1, s);
     MI_HIP(hipStreamSynchronize(s));
     const size_t n_kept = (size_t)indptr[h->n_items];
     *nnz = (long long)n_kept;
     if (n_kept) {
-        d_indices.download(indices, n_kept, s);
-        val2_sorted.download(data, n_kept, s);
+        w.d_indices.download(indices, n_kept, s);
+        w.val2_sorted.download(data, n_kept, s);
     }
-    if (nbr_idx) d_idx.download(nbr_idx, n_slots, s);
-    if (nbr_val) d_val.download(nbr_val, n_slots, s);
+    if (nbr_idx) w.d_idx.download(nbr_idx, w.n_slots, s);
+    if (nbr_val) w.d_val.download(nbr_val, w.n_slots, s);
     MI_HIP(hipStreamSynchronize(s));
+}
+
+// mi355rec_spscorer_update_from_slim: the first half again, with the sparse scorer's spare buffers in the place of the host
+template <class T>
+void spscorer_update_typed(mi355rec_slim *h, mi355rec_spscorer *sc, int topK) {
+    hipStream_t s = h->stream;
+    spscorer_adopt_begin(sc, s);
+    WBuild w;
+    build_w_on_device<T>(h, topK, w);
+    const double store_bytes = h->cfg.symmetric ? (double)(h->G.count * sizeof(Granule)) : (double)h->S.count;
+    spscorer_adopt(sc, s, w.d_indptr.ptr, w.d_indices.ptr, w.val2_sorted.ptr, w.n_slots, store_bytes, W_BUILD_LAUNCHES);
 }
 
 template <class T>
@@ -835,6 +872,30 @@ extern "C" int mi355rec_slim_get_W_csr(mi355rec_slim_t h, int32_t topK, int32_t 
         if (h->f64) get_w_csr_typed<double>(h, topK, nbr_idx, nbr_val, indptr, indices, data, &n);
         else get_w_csr_typed<float>(h, topK, nbr_idx, nbr_val, indptr, indices, data, &n);
         *nnz = (int64_t)n;
+    });
+}
+
+// Lives here, as mi355rec_scorer_update_from_mf lives in mf.hip: it launches this file's own read-out.  The refusals come before the
+// device is touched; the scorer's stream is drained, the build and the copy are queued on this handle's stream behind its own work,
+// and that stream is waited for (spscorer_adopt_begin / spscorer_adopt, handoff.hip).
+extern "C" int mi355rec_spscorer_update_from_slim(mi355rec_spscorer_t scorer, mi355rec_slim_t h, int32_t topK) {
+    return guarded([&] {
+        MI_REQUIRE(scorer && h, "NULL handle");
+        MI_REQUIRE(h->n_items == scorer->n_mid && h->n_items == scorer->n_items,
+                   "the SLIM handle has %d items, the scorer's B is %d x %d (an item-based scorer over the same items is needed)", h->n_items,
+                   scorer->n_mid, scorer->n_items);
+        MI_REQUIRE(topK >= 1, "topK must be >= 1");
+        if (h->cfg.train_with_sparse_weights)
+            fail(MI355REC_E_UNSUPPORTED, "a SLIM handle created with train_with_sparse_weights cannot be handed to a scorer: reading its model "
+                                         "prunes it");
+        if (h->n_items > 65535)
+            fail(MI355REC_E_UNSUPPORTED, "n_items = %d: the device-side column selection packs items into 16 bits", h->n_items);
+        require_consistent(h);
+        enter_call(h);
+        ReleaseScope scope(h->stream, h->side, scorer->stream);
+        topK = std::min(topK, h->n_items);
+        if (topK > MAX_TOPK) fail(MI355REC_E_UNSUPPORTED, "topK = %d exceeds the in-LDS selection limit of %d", topK, MAX_TOPK);
+        if (h->f64) spscorer_update_typed<double>(h, scorer, topK); else spscorer_update_typed<float>(h, scorer, topK);
     });
 }
 

@@ -12,8 +12,8 @@
 //                         whole profile in storage order, adds the cells of B's rows that fall inside the slice, and stores the slice
 //                         to the row in HBM.  Nobody else touches those cells, so the workgroup needs no barrier at all.  B's rows are
 //                         strictly ascending (checked when the mode is switched on), so "the part of row m inside slice k" is a
-//                         range cuts[m][k] .. cuts[m][k + 1] of the row, found once by binary search when the mode is switched on
-//                         (spexact_cuts_kernel).  The wavefront takes 64 profile cells at a time: their pieces of B are laid end to
+//                         range cuts[m][k] .. cuts[m][k + 1] of the row, found by binary search when the mode is switched on and
+//                         again whenever B is replaced (spexact_cuts_kernel, spexact_check_and_cut).  The wavefront takes 64 profile cells at a time: their pieces of B are laid end to
 //                         end, every lane loads and multiplies one cell of that sequence (all loads in flight together), then the
 //                         pieces are added to the slice one profile cell after the other.
 //   spexact_cand_kernel   candidate rows: the candidates are gathered from the full exact rows (a candidate's score IS the row's cell),
@@ -230,6 +230,38 @@ Ranking spexact_enqueue_candidates(mi355rec_spscorer *h, const int *users, int n
     return Ranking{h->ranked.ptr, s};
 }
 
+// The pass of exact mode over a B on the device -- the live one (set_exact) or one in the spare buffers that is about to replace it
+// (update_b, update_from_slim: the table is a function of B and is swapped in together with it).  The caller holds a ReleaseScope
+// over `s`.
+void spexact_check_and_cut(mi355rec_spscorer *h, hipStream_t s, const int *b_ptr, const int *b_idx, DeviceBuffer<int> *cuts) {
+    DeviceBuffer<int> first_bad;
+    int bad = INT_MAX;
+    first_bad.upload(&bad, 1, s);
+    hipLaunchKernelGGL(spexact_check_kernel, dim3(div_up(h->n_mid, 4)), dim3(256), 0, s, b_ptr, b_idx, h->n_mid, h->n_items, first_bad.ptr);
+    MI_HIP(hipGetLastError());
+    first_bad.download(&bad, 1, s);
+    MI_HIP(hipStreamSynchronize(s));
+    MI_REQUIRE(bad == INT_MAX, "exact mode: row %d of B does not hold its column ids strictly ascending inside [0, %d) (a column twice, or unsorted)",
+               bad, h->n_items);
+    if (!cuts) return;
+    const int tile = std::min(h->n_items, SPEXACT_TILE), slice = div_up(tile, SPEXACT_OWNERS);
+    const int tiles = div_up(h->n_items, tile);
+    if (tiles > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d items: at most %d in exact mode", h->n_items, 65535 * SPEXACT_TILE);
+    const int n_slices = tiles * SPEXACT_OWNERS;
+    const size_t cells = (size_t)h->n_mid * (n_slices + 1);
+    if (cells > ((size_t)1 << 32)) fail(MI355REC_E_UNSUPPORTED, "exact mode: %d rows of B x %d slices of a score row do not fit its table", h->n_mid, n_slices);
+    cuts->alloc(cells);
+    hipLaunchKernelGGL(spexact_cuts_kernel, dim3(h->n_mid), dim3(64), 0, s, b_ptr, b_idx, n_slices, tile, slice, h->n_items, cuts->ptr);
+    MI_HIP(hipGetLastError());
+    MI_HIP(hipStreamSynchronize(s));
+}
+
+size_t spexact_table_cells(const mi355rec_spscorer *h) {
+    if (!h->exact) return 0;
+    const int tiles = div_up(h->n_items, std::min(h->n_items, SPEXACT_TILE));
+    return (size_t)h->n_mid * ((size_t)tiles * SPEXACT_OWNERS + 1);
+}
+
 }  // namespace mi355rec
 
 using namespace mi355rec;
@@ -244,31 +276,11 @@ extern "C" int mi355rec_spscorer_set_exact(mi355rec_spscorer_t h, int32_t exact)
         ensure_device();
         hipStream_t s = h->stream;
         ReleaseScope scope(s);
-        DeviceBuffer<int> first_bad;
-        int bad = INT_MAX;
-        first_bad.upload(&bad, 1, s);
-        hipLaunchKernelGGL(spexact_check_kernel, dim3(div_up(h->n_mid, 4)), dim3(256), 0, s, (const int *)h->b_ptr.ptr, (const int *)h->b_idx.ptr,
-                           h->n_mid, h->n_items, first_bad.ptr);
-        MI_HIP(hipGetLastError());
-        first_bad.download(&bad, 1, s);
-        MI_HIP(hipStreamSynchronize(s));
-        MI_REQUIRE(bad == INT_MAX, "exact mode: row %d of B does not hold its column ids strictly ascending inside [0, %d) (a column twice, or unsorted)",
-                   bad, h->n_items);
-        if (!h->cuts.count) {       // (B never changes: a second switch-on finds the table there)
-            const int tile = std::min(h->n_items, SPEXACT_TILE), slice = div_up(tile, SPEXACT_OWNERS);
-            const int tiles = div_up(h->n_items, tile);
-            if (tiles > 65535) fail(MI355REC_E_UNSUPPORTED, "score rows of %d items: at most %d in exact mode", h->n_items, 65535 * SPEXACT_TILE);
-            const int n_slices = tiles * SPEXACT_OWNERS;
-            const size_t cells = (size_t)h->n_mid * (n_slices + 1);
-            if (cells > ((size_t)1 << 32)) fail(MI355REC_E_UNSUPPORTED, "exact mode: %d rows of B x %d slices of a score row do not fit its table", h->n_mid, n_slices);
-            DeviceBuffer<int> cuts;
-            cuts.alloc(cells);
-            hipLaunchKernelGGL(spexact_cuts_kernel, dim3(h->n_mid), dim3(64), 0, s, (const int *)h->b_ptr.ptr, (const int *)h->b_idx.ptr, n_slices,
-                               tile, slice, h->n_items, cuts.ptr);
-            MI_HIP(hipGetLastError());
-            MI_HIP(hipStreamSynchronize(s));
-            h->cuts.swap(cuts);
-        }
+        // (the table of the B the scorer holds: a second switch-on finds it there; a call that replaces B replaces the table with it,
+        // or drops it while the mode is off)
+        DeviceBuffer<int> cuts;
+        spexact_check_and_cut(h, s, h->b_ptr.ptr, h->b_idx.ptr, h->cuts.count ? nullptr : &cuts);
+        if (!h->cuts.count) h->cuts.swap(cuts);
         h->exact = 1;
     });
 }

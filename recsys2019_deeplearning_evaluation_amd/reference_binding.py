@@ -35,7 +35,8 @@ from .matrix_factorization import _AsySVDLogic, _BPRLogic, _FunkSVDLogic
 from .nmf import _NMFLogic
 from .non_personalized import _GlobalEffectsLogic, _RandomLogic, _TopPopLogic
 from .pure_svd import _PureSVDItemLogic, _PureSVDLogic
-from .scoring import GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin, HandOffScoringMixin
+from .scoring import (GpuItemScoreMixin, GpuScoringMixin, GpuSimilarityScoringMixin, HandOffScoringMixin,
+                      HandOffSimilarityScoringMixin)
 from .slim_bpr import _SLIMLogic
 from .slim_elasticnet import _SLIMElasticNetLogic
 
@@ -51,12 +52,13 @@ def bind(BaseMatrixFactorizationRecommender, BaseItemSimilarityMatrixRecommender
     sim_score = (GpuSimilarityScoringMixin,) if device_scoring else ()
     # (the recommenders that train with validations: the scoring mixin that also serves validation_hand_off = "device")
     mf = ((HandOffScoringMixin,) if device_scoring else ()) + (BaseMatrixFactorizationRecommender, Incremental_Training_Early_Stopping)
+    slim_score = (HandOffSimilarityScoringMixin,) if device_scoring else ()
     table = {
         "MatrixFactorization_BPR_MI355X": (_BPRLogic,) + mf,
         "MatrixFactorization_FunkSVD_MI355X": (_FunkSVDLogic,) + mf,
         "MatrixFactorization_AsySVD_MI355X": (_AsySVDLogic,) + mf,
         "IALSRecommender": (_IALSLogic,) + mf,
-        "SLIM_BPR_MI355X": (_SLIMLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping),
+        "SLIM_BPR_MI355X": (_SLIMLogic,) + slim_score + (BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping),
         "SLIMElasticNetRecommender": (_SLIMElasticNetLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),
         "PureSVDRecommender": (_PureSVDLogic,) + mf_score + (BaseMatrixFactorizationRecommender,),
         "PureSVDItemRecommender": (_PureSVDItemLogic,) + sim_score + (BaseItemSimilarityMatrixRecommender,),

@@ -261,7 +261,7 @@ class ValidationHandOff:
         if not self._HAND_OFF_SUPPORTED:
             raise ValueError("{}: validation_hand_off = 'device' is not supported: the user factors of this model are estimated on "
                              "the host".format(type(self).__name__))
-        if not isinstance(self, HandOffScoringMixin):
+        if not getattr(self, "_HAND_OFF_SCORER", False):    # (set by the scorer's half: HandOffScoringMixin, HandOffSimilarityScoringMixin)
             raise ValueError("{}: validation_hand_off = 'device' needs the device scorer (HandOffScoringMixin)".format(type(self).__name__))
         return True
 
@@ -284,6 +284,7 @@ class ValidationHandOff:
 class HandOffScoringMixin(GpuScoringMixin):
     """GpuScoringMixin for the recommenders with a ValidationHandOff logic class: the scorer's half of device mode.  With the flags
     clear -- host mode, and device mode outside a fit -- every method is its parent's."""
+    _HAND_OFF_SCORER = True         # what ValidationHandOff._hand_off_on_device looks for
     _host_model_stale = False
     _scorer_current = False
 
@@ -341,7 +342,7 @@ class MI355XSparseScorer(_Scorer):
     def __init__(self, A, B, URM_seen, exact=False):
         A, B, seen = A.tocsr(), B.tocsr(), URM_seen.tocsr()
         assert A.shape[1] == B.shape[0] and seen.shape == (A.shape[0], B.shape[1])
-        self.n_users, self.n_items = A.shape[0], B.shape[1]
+        self.n_users, self.n_mid, self.n_items = A.shape[0], B.shape[0], B.shape[1]
         self.exact = bool(exact)
         if self.exact and not B.has_sorted_indices:
             B = B.sorted_indices()      # (a copy: the caller's matrix stays as it is)
@@ -354,6 +355,39 @@ class MI355XSparseScorer(_Scorer):
             except ValueError:
                 self.close()
                 raise
+
+    def update_B(self, B):
+        """Another B of the same shape, with any number of stored cells, in the place of the one the scorer holds; A and the seen CSR
+        stay on the device.  B is treated as the constructor treats it (`tocsr()`, sorted indices in exact mode); afterwards the scorer
+        answers as one built from (A, B) would.  ValueError naming the first offending row -- row pointers that do not start at 0 or
+        decrease, a column id outside [0, n_items), in exact mode a column stored twice in a row -- and the scorer keeps the B it had."""
+        B = B.tocsr()
+        if B.shape != (self.n_mid, self.n_items):
+            raise ValueError("B is {}, the scorer's is {}".format(B.shape, (self.n_mid, self.n_items)))
+        if self.exact and not B.has_sorted_indices:
+            B = B.sorted_indices()
+        arrs = [N.as_i32(B.indptr), N.as_i32(B.indices), N.as_f32(B.data)]
+        self._call("update_b", *[N.ptr(a) if len(a) else N.ptr(np.zeros(1, a.dtype)) for a in arrs])
+
+    def weights(self):
+        """B as the scorer holds it on the device, a csr_matrix (n_mid x n_items, float32): its arrays cell for cell."""
+        indptr, nnz = np.empty(self.n_mid + 1, np.int32), C.c_int64(0)
+        self._call("get_b", N.ptr(indptr), None, None, C.byref(nnz))
+        indices, data = np.empty(max(1, nnz.value), np.int32), np.empty(max(1, nnz.value), np.float32)
+        self._call("get_b", N.ptr(indptr), N.ptr(indices), N.ptr(data), C.byref(nnz))
+        return sps.csr_matrix((data[:nnz.value], indices[:nnz.value], indptr), shape=(self.n_mid, self.n_items))
+
+    def update_from(self, slim_epoch):
+        """B <- similarityMatrixTopK(get_S(), topK) of a SLIM_BPR_MI355X_Epoch, the W its `get_S_and_W()` returns, array for array,
+        built and copied on the device: no download, no SciPy matrix, no new scorer.  TypeError for any other object; ValueError for
+        a closed handle, for one over other items than the scorer's B (a user-based scorer) and for a topK below 1;
+        NotImplementedError for the sparse store (train_with_sparse_weights).  A refused call leaves the scorer as it was."""
+        from .slim_bpr import SLIM_BPR_MI355X_Epoch
+        if not isinstance(slim_epoch, SLIM_BPR_MI355X_Epoch):
+            raise TypeError("update_from takes a SLIM_BPR_MI355X_Epoch, got {}".format(type(slim_epoch).__name__))
+        if not slim_epoch._h:
+            raise ValueError("%s is closed" % type(slim_epoch).__name__)
+        self._call("update_from_slim", slim_epoch._h, int(slim_epoch.topK or 0))
 
 
 class MI355XDenseScorer(_Scorer):
@@ -397,8 +431,9 @@ class MI355XDenseScorer(_Scorer):
 
 class GpuSimilarityScoringMixin(_ScoringMixin):
     """recommend() for BaseItemSimilarityMatrixRecommender / BaseUserSimilarityMatrixRecommender subclasses, served by
-    MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  The sparse scorer has no update: it is rebuilt whenever
-    W_sparse or URM_train is replaced (fit, early-stopping validation) or W_sparse changes in place.
+    MI355XSparseScorer.  `_SCORER_USER_BASED` selects the operand order.  Under this cache rule the scorer is rebuilt whenever
+    W_sparse or URM_train is replaced (fit, early-stopping validation) or W_sparse changes in place; replacing its B in place
+    (`MI355XSparseScorer.update_B` / `update_from`) is what HandOffSimilarityScoringMixin does during a device-mode fit.
 
     An item-based model whose W_sparse is a dense ndarray is served by MI355XDenseScorer when the class (or the object) sets
     `dense_scoring = "device"`; with the default "host" it is scored by the base class on the host, as before.  The dense scorer has a
@@ -468,6 +503,69 @@ class GpuSimilarityScoringMixin(_ScoringMixin):
     def release_dense_scorer(self):
         """Give the dense scorer's n_items^2 floats of HBM back (a sparse W_sparse after a dense one)."""
         self._drop_scorer(self._SCORER_ATTRS[1])
+
+
+class HandOffSimilarityScoringMixin(GpuSimilarityScoringMixin):
+    """GpuSimilarityScoringMixin for a recommender with a ValidationHandOff logic class whose training handle can fill the sparse
+    scorer (SLIM-BPR): the scorer's half of `validation_hand_off = "device"`, as HandOffScoringMixin is for the factor models.  With
+    the flags clear -- host mode, and device mode outside a fit -- every method is its parent's.
+
+    While `_host_model_stale` is set, W_sparse and S_incremental are the matrices of the last validation that was synced -- the
+    first of the fit, or the last one before a `_sync_host_model()` -- not of the one being validated: code that reads `rec.W_sparse`
+    directly in the middle of a device-mode fit sees that older matrix.  `_compute_item_score`, `save_model` and `invalidate_scorer`
+    sync first."""
+    _HAND_OFF_SCORER = True
+    _host_model_stale = False
+    _scorer_current = False
+
+    def _hand_off_model(self):
+        """_prepare_model_for_validation of device mode.  The first validation of a fit runs the host path as it stands -- which is
+        also the one upload of URM_train and the seen CSR; from then on the scorer's B is replaced from the training handle."""
+        if self._scorer_current and self._hand_off_scorer() is not None:
+            self._sp_scorer.update_from(self.epoch_kernel)
+            self._host_model_stale = True
+            return
+        self._download_model()
+        self._host_model_stale = False
+        self._get_sparse_scorer()
+        self._scorer_current = True
+
+    def _hand_off_scorer(self):
+        """The sparse scorer while it can go on being filled from the training handle: same URM_train, same scoring mode."""
+        scorer = self._sp_scorer
+        if scorer is not None and self._sp_scorer_src["urm"] is self.URM_train and scorer.exact == self._sparse_scoring_exact():
+            return scorer
+        return None
+
+    def _sync_host_model(self):
+        """W_sparse and S_incremental <- the model that is being validated, if they are stale; nothing is downloaded otherwise."""
+        if self._host_model_stale:
+            self._download_model()
+            self._host_model_stale = False
+
+    def device_scorer(self):
+        if self._scorer_current:
+            scorer = self._hand_off_scorer()
+            if scorer is not None:
+                return scorer
+            self._sync_host_model()             # (URM_train or sparse_scoring changed mid-fit: back to the cache rule, which builds a new scorer)
+            self._scorer_current = False
+        return super(HandOffSimilarityScoringMixin, self).device_scorer()
+
+    def invalidate_scorer(self):
+        if self._host_model_stale and getattr(getattr(self, "epoch_kernel", None), "_h", None):
+            self._sync_host_model()             # (the scorer held the only copy of the validated W outside the training handle)
+        self._host_model_stale = False
+        self._scorer_current = False
+        super(HandOffSimilarityScoringMixin, self).invalidate_scorer()
+
+    def _compute_item_score(self, user_id_array, items_to_compute=None):
+        self._sync_host_model()
+        return super(HandOffSimilarityScoringMixin, self)._compute_item_score(user_id_array, items_to_compute=items_to_compute)
+
+    def save_model(self, folder_path, file_name=None):
+        self._sync_host_model()
+        return super(HandOffSimilarityScoringMixin, self).save_model(folder_path, file_name=file_name)
 
 
 class MI355XItemScorer(_Scorer):

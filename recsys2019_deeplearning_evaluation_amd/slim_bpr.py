@@ -20,7 +20,7 @@ import scipy.sparse as sps
 from . import _native as N
 from .recommender_base import (BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping, check_matrix,
                                similarityMatrixTopK)
-from .scoring import GpuSimilarityScoringMixin
+from .scoring import HandOffSimilarityScoringMixin, ValidationHandOff
 
 
 def rows_slabs_to_csr(nbr_idx, nbr_val, n):
@@ -147,8 +147,15 @@ class SLIM_BPR_MI355X_Epoch(N.Handle):
         return a.value, b.value
 
 
-class _SLIMLogic:
-    """Drop-in for SLIM_BPR_Cython."""
+class _SLIMLogic(ValidationHandOff):
+    """Drop-in for SLIM_BPR_Cython.
+
+    `validation_hand_off` (scoring.ValidationHandOff): "host", the default -- every validation downloads S and W, assembles two SciPy
+    matrices and a new scorer uploads URM_train, the seen CSR and W -- or "device": after the first validation of a fit, which runs
+    that path once, the scorer's B is replaced from the training handle on the device (`MI355XSparseScorer.update_from`) and
+    W_sparse / S_incremental are only marked stale (scoring.HandOffSimilarityScoringMixin: reads of `W_sparse` in the middle of such a
+    fit see the last synced matrix).  Device mode is refused at fit, before the device is touched, for train_with_sparse_weights=True
+    (reading that store's model prunes it), topK=False (W is the dense S) and more than 65 535 items."""
     RECOMMENDER_NAME = "SLIM_BPR_Recommender"
 
     def __init__(self, URM_train, verbose=True, free_mem_threshold=0.5):
@@ -161,6 +168,8 @@ class _SLIMLogic:
     def fit(self, epochs=300, positive_threshold_BPR=None, train_with_sparse_weights=None, symmetric=True, random_seed=None,
             batch_size=1000, lambda_i=0.0, lambda_j=0.0, learning_rate=1e-4, topK=200, sgd_mode="adagrad", gamma=0.995,
             beta_1=0.9, beta_2=0.999, **earlystopping_kwargs):
+        if self._begin_hand_off():              # (an unknown mode, or "device" where it cannot be, is refused before the device is touched)
+            self._check_device_hand_off(train_with_sparse_weights, topK)
         self.symmetric = symmetric
         # the reference picks dense vs sparse-tree from free host RAM (.py:97-114); on the device S always lives
         # densely in HBM (288 GB), so "auto" means dense.  train_with_sparse_weights=True selects the sparse store's
@@ -191,13 +200,34 @@ class _SLIMLogic:
         self.S_best = self.S_incremental.copy()
         self._train_with_early_stopping(epochs, algorithm_name=self.RECOMMENDER_NAME, **earlystopping_kwargs)
         self.get_S_incremental_and_set_W()
+        self._end_hand_off()
         self.epoch_kernel._dealloc()
         sys.stdout.flush()
 
+    def _check_device_hand_off(self, train_with_sparse_weights, topK):
+        name = type(self).__name__
+        if train_with_sparse_weights:
+            raise ValueError("{}: validation_hand_off = 'device' does not serve train_with_sparse_weights=True: reading that store's "
+                             "model prunes it, so a validation must read it exactly once".format(name))
+        if not topK:
+            raise ValueError("{}: validation_hand_off = 'device' needs a topK: with topK=False W_sparse is the dense S".format(name))
+        if self.URM_train.shape[1] > 65535:
+            raise ValueError("{}: validation_hand_off = 'device' serves at most 65535 items (the device-side column selection), "
+                             "URM_train has {}".format(name, self.URM_train.shape[1]))
+
+    def _download_model(self):
+        self.get_S_incremental_and_set_W()
+
     def _prepare_model_for_validation(self):
+        if self._hand_off_on_device():
+            return self._hand_off_model()
         self.get_S_incremental_and_set_W()
 
     def _update_best_model(self):
+        if self._host_model_stale:
+            # device mode: the dense and symmetric stores' get_S only reads and the handle has not advanced since the validation, so
+            # this is the matrix host mode copies here, dtype included
+            self.S_incremental = self.epoch_kernel.get_S()
         self.S_best = self.S_incremental.copy()
 
     def _run_epoch(self, num_epoch):
@@ -218,5 +248,5 @@ class _SLIMLogic:
         self.W_sparse = check_matrix(self.W_sparse, format="csr")
 
 
-class SLIM_BPR_MI355X(_SLIMLogic, GpuSimilarityScoringMixin, BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping):
+class SLIM_BPR_MI355X(_SLIMLogic, HandOffSimilarityScoringMixin, BaseItemSimilarityMatrixRecommender, Incremental_Training_Early_Stopping):
     pass
