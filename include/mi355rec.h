@@ -302,6 +302,21 @@ int mi355rec_mf_get_factors(mi355rec_mf_t h, float *U, float *V, float *bu, floa
 /* The same as float64, the type the reference's getters return (.pyx:685-702): the device state itself when it is float64
  * (adagrad / rmsprop / adam, AsySVD), the float32 state widened otherwise. */
 int mi355rec_mf_get_factors_f64(mi355rec_mf_t h, double *U, double *V, double *bu, double *bi, double *mu);
+/* AsySVD's user factors from the handle's own URM and its Y, on the device (MatrixFactorization_Cython.py:281-304,
+ * _estimate_user_factors): out[u, f] = (sum over the profile of u, in the handle's storage order -- sorted ids -- of
+ * (double)rating * Y[item, f]) / row_divisor[u], SciPy's csr_matvecs recurrence in float64 bit for bit (every product and every sum
+ * rounded on its own, starting from +0.0) and one IEEE division.  row_divisor (n_users, host) is the caller's:
+ * sqrt(profile length) computed on the host; a row whose divisor is not above 0 is left undivided, +0.0 for an empty profile.
+ * out is n_users x k float64 on the host.  Queued on the handle's stream behind its training work; the handle's state is not
+ * changed.  MI355REC_E_UNSUPPORTED for a handle that is not ASY_SVD or whose state is float32.
+ * Stats: kernel_ms the one launch, call_ms with the copies around it, algorithmic_bytes = nnz (8 k + 8) + 8 n_users k. */
+int mi355rec_mf_asy_user_factors(mi355rec_mf_t h, const double *row_divisor, double *out);
+/* The same without a handle (the cold users of a new URM, after the training handle is closed): uploads, runs the same kernel,
+ * downloads.  Rows are summed in the order they are stored, sorted or not.  Y is n_items x k float64, k as an ASY_SVD handle takes
+ * it.  Row pointers that do not climb from 0, or a column id outside [0, n_items), are MI355REC_E_INVALID: nothing is run and out
+ * is not written. */
+int mi355rec_asy_user_factors(int32_t n_rows, int32_t n_items, int32_t k, const int32_t *indptr, const int32_t *indices,
+                              const float *data, const double *Y, const double *row_divisor, double *out);
 /* Copy the (u, i, j|rating) stream drawn by the LAST mi355rec_mf_run_epochs call (at most cap entries);
  * returns the number of samples of that call in *n. */
 int mi355rec_mf_get_last_samples(mi355rec_mf_t h, int32_t *u, int32_t *i, int32_t *j, float *rating, int64_t cap, int64_t *n);

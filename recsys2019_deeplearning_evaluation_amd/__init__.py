@@ -12,7 +12,7 @@ from .knn_cbf import (ItemKNNCBFRecommender, UserKNNCBFRecommender, ItemKNN_CFCB
                       UserKNN_CFCBF_Hybrid_Recommender, ItemKNNCustomSimilarityRecommender)
 from .matrix_factorization import (MatrixFactorization_MI355X_Epoch, MatrixFactorization_BPR_MI355X,  # noqa: F401
                                    MatrixFactorization_FunkSVD_MI355X, MatrixFactorization_AsySVD_MI355X,
-                                   MatrixFactorization_MI355X_Group)
+                                   MatrixFactorization_MI355X_Group, asysvd_user_factors)
 
 from .slim_bpr import SLIM_BPR_MI355X_Epoch, SLIM_BPR_MI355X  # noqa: F401,E402
 from .scoring import (MI355XScorer, MI355XSparseScorer, MI355XDenseScorer, MI355XItemScorer, GpuScoringMixin, GpuSimilarityScoringMixin,  # noqa: F401,E402
@@ -27,4 +27,4 @@ from .nmf import NMFRecommender  # noqa: F401,E402
 from .non_personalized import TopPop, GlobalEffects, Random  # noqa: F401,E402
 
 __all__ = ["MI355XDenseScorer", "TopPop", "GlobalEffects", "Random", "MI355XItemScorer", "GpuItemScoreMixin", "ResidentURM", "ResidentStack", "ItemKNNCBFRecommender", "UserKNNCBFRecommender", "ItemKNN_CFCBF_Hybrid_Recommender", "UserKNN_CFCBF_Hybrid_Recommender", "ItemKNNCustomSimilarityRecommender", "PureSVDRecommender", "PureSVDItemRecommender", "NMFRecommender", "EvaluatorHoldout_MI355X", "EvaluatorNegativeItemSample_MI355X", "EASE_R_Recommender", "EASE_R_MI355X_Recommender", "MI355XEase", "SLIMElasticNetRecommender", "P3alphaRecommender", "RP3betaRecommender", "MI355XScorer", "MI355XSparseScorer", "GpuScoringMixin", "GpuSimilarityScoringMixin", "SLIM_BPR_MI355X_Epoch", "SLIM_BPR_MI355X", "IALS_MI355X_Epoch", "IALSRecommender", "Compute_Similarity", "Compute_Similarity_MI355X", "Compute_Similarity_Euclidean_MI355X", "ItemKNNCFRecommender", "UserKNNCFRecommender",
-           "MatrixFactorization_MI355X_Epoch", "MatrixFactorization_MI355X_Group", "MatrixFactorization_BPR_MI355X", "MatrixFactorization_FunkSVD_MI355X", "MatrixFactorization_AsySVD_MI355X"]
+           "MatrixFactorization_MI355X_Epoch", "MatrixFactorization_MI355X_Group", "MatrixFactorization_BPR_MI355X", "MatrixFactorization_FunkSVD_MI355X", "MatrixFactorization_AsySVD_MI355X", "asysvd_user_factors"]

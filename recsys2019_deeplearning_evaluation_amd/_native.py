@@ -116,6 +116,8 @@ SIGNATURES = {
     "mi355rec_mf_shard_end_epoch": (C.c_int, [_vp]),
     "mi355rec_mf_get_factors": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355rec_mf_get_factors_f64": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "mi355rec_mf_asy_user_factors": (C.c_int, [_vp, _vp, _vp]),
+    "mi355rec_asy_user_factors": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mi355rec_mf_get_last_samples": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "mi355rec_mf_set_profiling": (C.c_int, [_vp, _i32]),
     "mi355rec_mf_get_phase_ticks": (C.c_int, [_vp, _vp, _i64, C.POINTER(_i64)]),

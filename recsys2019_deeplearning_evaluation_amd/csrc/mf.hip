@@ -38,6 +38,8 @@
 // There is no dense contraction here, hence no MFMA.
 #include "common.h"
 #include "score.h"
+#include "asy_estimate.h"
+#include "asy_estimate_plan.h"
 #include "sampling.cuh"
 #include "wave.cuh"
 
@@ -72,6 +74,7 @@ struct mi355rec_mf : Handle {
     DeviceBuffer<double> loss_slots;
     DeviceBuffer<MfState> state;
     DeviceBuffer<unsigned long long> ticks;         // MI355REC_MF_TICKS: the mini-batch kernel's phase stamps
+    DeviceBuffer<int> asy_order;                    // mi355rec_mf_asy_user_factors: the users longest profile first, made by its first call
     long long batches_done = 0;      // batches executed since create (device state mirrors this)
     long long last_call_samples = 0; // samples in the stream buffer after the last native call
     int max_timed = 0;
@@ -1338,6 +1341,47 @@ extern "C" int mi355rec_mf_get_factors_f64(mi355rec_mf_t h, double *U, double *V
         MI_REQUIRE(h, "NULL handle");
         ensure_device();
         if (h->f64) get_factors_typed<double, double>(h, U, V, bu, bi, mu); else get_factors_typed<float, double>(h, U, V, bu, bi, mu);
+    });
+}
+
+// Host code only: the handle struct is private to this file, the kernel is asy_estimate.hip's.
+extern "C" int mi355rec_mf_asy_user_factors(mi355rec_mf_t h, const double *row_divisor, double *out) {
+    static_assert(asy_estimate_plan::KMAX == ASY_KMAX, "the estimate takes every k an ASY_SVD handle takes");
+    return guarded([&] {
+        MI_REQUIRE(h && row_divisor && out, "NULL argument");
+        if (h->cfg.algorithm != MI355REC_MF_ASY_SVD)
+            fail(MI355REC_E_UNSUPPORTED, "user factors are estimated from Y for ASY_SVD only: this handle's user factors are its model");
+        if (!h->f64) fail(MI355REC_E_UNSUPPORTED, "the user-factor estimate is float64 arithmetic: this ASY_SVD handle keeps its state in float32");
+        ensure_device();
+        hipStream_t s = h->stream;
+        ReleaseScope scope(s);
+        if (!h->asy_order.count) {
+            std::vector<int32_t> indptr((size_t)h->n_users + 1);
+            h->indptr.download(indptr.data(), indptr.size(), s);
+            MI_HIP(hipStreamSynchronize(s));
+            asy_estimate_upload_order(h->n_users, indptr.data(), h->asy_order, s);
+        }
+        MfParams<double> p{};
+        fill_params(h, p);              // (Y is p.U0: AsySVD never flips a buffer)
+        DeviceBuffer<double> divisor, estimate;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        h->dispatch_timers.reserve(1);
+        h->dispatch_timers.reset();
+        h->dispatch_timers.next(e0, e1, 1);
+        h->timer.start(s);
+        divisor.upload(row_divisor, (size_t)h->n_users, s);
+        estimate.alloc((size_t)h->n_users * h->k);
+        asy_estimate_enqueue(h->n_users, h->k, {h->indptr.ptr, h->indices.ptr, h->data.ptr, p.U0, divisor.ptr, h->asy_order.ptr, estimate.ptr}, s,
+                             e0, e1);
+        estimate.download(out, estimate.count, s);
+        h->timer.stop(s);
+        MI_HIP(hipStreamSynchronize(s));
+        h->stats = mi355rec_stats{};
+        h->stats.call_ms = h->timer.elapsed_ms();
+        h->stats.kernel_ms = h->dispatch_timers.total_ms();
+        h->stats.n_launches = h->stats.n_timed = 1;
+        h->stats.n_units = (int64_t)h->n_users * h->k;
+        h->stats.algorithmic_bytes = asy_estimate_plan::bytes((long long)h->nnz, h->n_users, h->k);
     });
 }
 

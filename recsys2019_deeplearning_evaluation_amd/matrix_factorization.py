@@ -11,7 +11,10 @@ for U then V, .pyx:142-175).  On the device factors and optimiser moments are fl
 adagrad / rmsprop / adam (`precision="auto"`; the reference computes in double and the adaptive normalisation amplifies
 float32 rounding); the getters return float32 either way.  Sampling happens on the device
 (counter-based RNG seeded by random_seed); `replay_samples` runs the identical arithmetic on a given sample
-stream (parity mode).  AsySVD ("ASY_SVD", batch_size 1) runs its steps strictly in order on one workgroup.
+stream (parity mode).  AsySVD ("ASY_SVD", batch_size 1) runs its steps strictly in order on one workgroup; its user factors --
+URM . Y, every row divided by sqrt(profile length) -- are estimated on the host as the reference does, or, with
+`user_factor_estimate = "device"`, by a kernel that repeats SciPy's float64 arithmetic bit for bit (`estimate_user_factors`,
+`asysvd_user_factors`).
 """
 import ctypes as C
 import sys
@@ -80,6 +83,7 @@ class MatrixFactorization_MI355X_Epoch(N.Handle):
                          negative_reg, negative_interactions_quota, gamma, beta_1, beta_2, seed & (2 ** 64 - 1),
                          N.PRECISION_CODES[precision], 0)
         indptr, indices, data = N.as_i32(URM_train.indptr), N.as_i32(URM_train.indices), N.as_f32(URM_train.data)
+        self._indptr = indptr                   # (estimate_user_factors: the profile lengths of the URM the handle holds)
         U0, V0 = (N.as_f64(U0), N.as_f64(V0)) if precision == "fp64" else (N.as_f32(U0), N.as_f32(V0))
         self._create(C.byref(cfg), self.n_users, self.n_items, N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(U0), N.ptr(V0))
 
@@ -160,6 +164,47 @@ class MatrixFactorization_MI355X_Epoch(N.Handle):
 
     def get_GLOBAL_bias(self):
         return np.array(self._download(True)[4][0])
+
+    # ---- AsySVD: the user factors, estimated from Y on the device ----
+    def estimate_user_factors(self, row_divisor=None):
+        """AsySVD's USER_factors (n_users x k float64) from the handle's URM and its Y as it stands: bit for bit
+        `URM.dot(get_USER_factors())` with every row divided by row_divisor -- by default sqrt(profile length) of the handle's URM,
+        computed here on the host; a row whose divisor is 0 is left undivided (an empty profile: +0.0).  The handle's URM has sorted
+        indices, so the sums run in that order.  Training may go on afterwards: nothing of the handle's state changes.
+        ValueError unless the handle is ASY_SVD with float64 state."""
+        if self.algorithm_name != "ASY_SVD" or self.precision != "fp64":
+            raise ValueError("estimate_user_factors: user factors are estimated from Y for algorithm_name 'ASY_SVD' with precision 'fp64' "
+                             "only, this handle is '{}' in '{}'".format(self.algorithm_name, self.precision))
+        if row_divisor is None:
+            row_divisor = np.sqrt(np.ediff1d(self._indptr))
+        row_divisor = N.as_f64(row_divisor)
+        if row_divisor.shape != (self.n_users,):
+            raise ValueError("estimate_user_factors: row_divisor has shape {}, the URM {} users".format(row_divisor.shape, self.n_users))
+        out = np.empty((self.n_users, self.n_factors), np.float64)
+        self._call("asy_user_factors", N.ptr(row_divisor), N.ptr(out))
+        return out
+
+
+def asysvd_user_factors(URM, ITEM_factors_Y):
+    """AsySVD's USER_factors for any URM and a learned Y (n_items x k) on the device, without a training handle: bit for bit
+    `URM.dot(Y)` in float64 with every row divided by sqrt(profile length) -- _AsySVDLogic._estimate_user_factors.  The cells of a row
+    are summed in the order the CSR stores them, sorted or not, as SciPy does.  The device holds the ratings as float32: a URM whose
+    values float32 cannot hold is a ValueError (the host estimate is there for it)."""
+    URM = check_matrix(URM, "csr")
+    Y = N.as_f64(ITEM_factors_Y)
+    if Y.ndim != 2 or Y.shape[0] != URM.shape[1]:
+        raise ValueError("asysvd_user_factors: ITEM_factors_Y has shape {}, the URM {} items".format(Y.shape, URM.shape[1]))
+    data = N.as_f32(URM.data)
+    if URM.data.dtype != np.float32 and not np.array_equal(data, URM.data):
+        raise ValueError("asysvd_user_factors: the URM holds {} values that float32 does not represent".format(URM.data.dtype))
+    if URM.nnz > 2 ** 31 - 1:
+        raise ValueError("asysvd_user_factors: {} cells do not fit int32 row pointers".format(URM.nnz))
+    indptr, indices = N.as_i32(URM.indptr), N.as_i32(URM.indices)
+    row_divisor = np.sqrt(np.ediff1d(URM.indptr))
+    out = np.empty((URM.shape[0], Y.shape[1]), np.float64)
+    N.check(N.load().mi355rec_asy_user_factors(URM.shape[0], URM.shape[1], Y.shape[1], N.ptr(indptr), N.ptr(indices), N.ptr(data), N.ptr(Y),
+                                               N.ptr(N.as_f64(row_divisor)), N.ptr(out)))
+    return out
 
 
 class MatrixFactorization_MI355X_Group(N.Handle):
@@ -316,9 +361,16 @@ class _FunkSVDLogic(_MatrixFactorizationLogic):
 
 class _AsySVDLogic(_MatrixFactorizationLogic):
     """Drop-in for MatrixFactorization_AsySVD_Cython (MatrixFactorization_Cython.py:219): two item-sized factor matrices;
-    a user's factors are the sum of the Y rows of its profile divided by sqrt(profile length)."""
+    a user's factors are the sum of the Y rows of its profile divided by sqrt(profile length).
+
+    `user_factor_estimate` (class or object attribute) is "host", the default -- that estimate is SciPy's `URM_train.dot(Y)` before
+    every validation, as in the reference -- or "device": the same numbers, bit for bit, from the training handle's URM and Y in HBM
+    (`estimate_user_factors`), or from `asysvd_user_factors` where the handle's sorted copy of the URM would sum in another order than
+    `URM_train` stores, and for the cold users of `set_URM_train`.  Y, V and the biases are downloaded in both modes."""
     RECOMMENDER_NAME = "MatrixFactorization_AsySVD_MI355X_Recommender"
     _HAND_OFF_SUPPORTED = False       # validation_hand_off = "device" is a ValueError at fit: USER_factors are estimated on the host
+    USER_FACTOR_ESTIMATE_MODES = ("host", "device")
+    user_factor_estimate = "host"
 
     def __init__(self, *pos_args, **key_args):
         super(_AsySVDLogic, self).__init__(*pos_args, algorithm_name="ASY_SVD", **key_args)
@@ -327,11 +379,26 @@ class _AsySVDLogic(_MatrixFactorizationLogic):
         if key_args.get("batch_size", 1) > 1:
             print("{}: batch_size not supported for this recommender, setting to default value 1.".format(self.RECOMMENDER_NAME))
         key_args["batch_size"] = 1
+        self._estimate_on_device()              # (an unknown mode is refused before the device is touched)
         super(_AsySVDLogic, self).fit(**key_args)
 
+    def _estimate_on_device(self):
+        mode = self.user_factor_estimate
+        if mode not in self.USER_FACTOR_ESTIMATE_MODES:
+            raise ValueError("{}: user_factor_estimate must be one of {}, got {!r}".format(type(self).__name__,
+                                                                                         self.USER_FACTOR_ESTIMATE_MODES, mode))
+        return mode == "device"
+
     def _prepare_model_for_validation(self):
+        on_device = self._estimate_on_device()
         self.ITEM_factors_Y, self.ITEM_factors = self.epoch_kernel.get_factors()
-        self.USER_factors = self._estimate_user_factors(self.ITEM_factors_Y)
+        if not on_device:
+            self.USER_factors = self._estimate_user_factors(self.ITEM_factors_Y)
+        elif self.URM_train.has_sorted_indices and self.URM_train.dtype == np.float32:
+            self.USER_factors = self.epoch_kernel.estimate_user_factors()
+        else:
+            # the handle sorted (and narrowed) its copy; the host function sums URM_train's cells as URM_train stores them
+            self.USER_factors = asysvd_user_factors(self.URM_train, self.ITEM_factors_Y)
         self._forget_device_scorer()
         if self.use_bias:
             self.USER_bias = self.epoch_kernel.get_USER_bias()
@@ -348,7 +415,10 @@ class _AsySVDLogic(_MatrixFactorizationLogic):
         super(_AsySVDLogic, self).set_URM_train(URM_train_new, **kwargs)
         if estimate_item_similarity_for_cold_users:           # (sic: the reference's keyword; it re-estimates USER_factors)
             self._print("Estimating USER_factors for cold users...")
-            self.USER_factors = self._estimate_user_factors(self.ITEM_factors_Y_best)
+            if self._estimate_on_device():      # (the training handle is closed by now, and this is another URM)
+                self.USER_factors = asysvd_user_factors(self.URM_train, self.ITEM_factors_Y_best)
+            else:
+                self.USER_factors = self._estimate_user_factors(self.ITEM_factors_Y_best)
             self._print("Estimating USER_factors for cold users... done!")
 
     def _estimate_user_factors(self, ITEM_factors_Y):
